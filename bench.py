@@ -80,7 +80,32 @@ def parse():
     ap.add_argument("--no-fp8-point", action="store_true", help="skip the batch-64 timing of the fp8 (e4m3 resnet convs) engine in the default run")
     ap.add_argument("--no-driver-points", action="store_true", help="skip path.config2_mixed / path.driver_e2e (driver.generate with LoRA switches, text encoder, PNG sink)")
     ap.add_argument("--cpu-baseline-threads", type=int, default=0, help="0 = all cores of the host (default); e.g. 8 for the build container's figure")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the images the last timed step returned to DIR/images.npy (float32, see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(d, images):
+    """The uint8 NHWC images one timed step returned (all ranks' after the all-gather), as float32 DIR/images.npy, and the batch
+    index of each stored image as float64 DIR/images_index.npy.  Images past the 64 MB budget are left out: the stored ones are a
+    fixed sample of the batch (numpy seed 0, ascending order), so two runs with the same arguments store the same images."""
+    import numpy as np
+    a = images.cpu().numpy()
+    n, per = a.shape[0], a[0].size * 4 + 8                          # float32 image + its float64 index
+    keep = min(n, (DUMP_BUDGET_BYTES - 4096) // per)                 # 4 KB for the two .npy headers
+    if keep < 1:
+        raise SystemExit(f"--dump-outputs: one {a.shape[1:]} image exceeds {DUMP_BUDGET_BYTES >> 20} MB as float32")
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "images.npy"), a[idx].astype(np.float32))
+    np.save(os.path.join(d, "images_index.npy"), idx.astype(np.float64))
+    print(f"--dump-outputs: {keep} of {n} images {a.shape[1:]} -> {d}/images.npy", file=sys.stderr, flush=True)
 
 
 def launch_ranks(n: int) -> int:
@@ -573,6 +598,7 @@ def main():
                 if force_dist and world == 1:
                     assert torch.equal(gathered, out.images), "all_gather_into_tensor at world size 1 must return the local images"
             return out.images
+        step.gathered = gathered
         return step, (pe, ne, noise)
 
     B = args.batch
@@ -585,6 +611,9 @@ def main():
         g2 = D.all_gather_images(img, [img.shape[0]] * world, force=True)         # driver.generate's collective on device tensors
         assert torch.equal(g2, img) if world == 1 else g2.shape[0] == world * img.shape[0]
     assert img.dtype == torch.uint8 and tuple(img.shape) == (B, args.size, args.size, 3)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's images, taken before the extra points below reuse the engine
+        dump_outputs(args.dump_outputs, step.gathered if step.gathered is not None else img)
 
     fl_unet, fl_vae = 2.0 * S.unet_macs(ucfg, lat_side), 2.0 * S.vae_decode_macs(vcfg, lat_side)
     flops_per_image = 2 * args.ddpm_steps * fl_unet + fl_vae

@@ -75,6 +75,9 @@ def load() -> C.CDLL:
     if not os.path.isfile(LIB_PATH):
         raise IdbError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        f"or `make -C faceposegenerator_amd/csrc` (there is no CPU fallback)")
+    # torch ships its own libamdhip64 under the same soname: loaded after torch, the library binds to torch's HIP runtime; loaded
+    # before it, the process maps two HIP (and HSA) runtimes and the one initialised second finds no device
+    import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
     sig = {

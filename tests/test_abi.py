@@ -75,3 +75,16 @@ def test_no_kernel_uses_scratch_or_spills(lib):
         if scratch or vspill:
             bad.append((name, scratch, vspill))
     assert not bad, bad
+
+
+def test_library_shares_torchs_hip_runtime(lib):
+    """Loaded before torch (build() then smoke() in one process), the library must still bind to torch's HIP runtime: a second
+    libamdhip64 / libhsa-runtime64 in the process finds no device once torch's has initialised."""
+    import subprocess
+    import sys
+    code = ("from faceposegenerator_amd import _lib; _lib.load(); import torch\n"
+            "print(sorted({l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l or 'libhsa-runtime64' in l}))")
+    p = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    maps = eval(p.stdout.strip().splitlines()[-1])
+    assert len([m for m in maps if "libamdhip64" in m]) == 1 and len([m for m in maps if "libhsa-runtime64" in m]) == 1, maps

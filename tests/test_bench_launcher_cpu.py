@@ -59,3 +59,45 @@ def test_forced_collectives_at_world_size_1_on_gloo():
     assert p.returncode == 0, p.stderr[-2000:]
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert r["n_gpus"] == 1 and r["config"]["forced_collectives"] == "gloo"
+
+
+def test_dump_outputs_writes_the_last_step_images_reproducibly(tmp_path):
+    """--dump-outputs DIR: the images of the last timed step as float32 DIR/images.npy (+ their batch indices), the same arrays
+    from two runs with the same arguments; with 2 ranks, rank 0 writes the all-gathered batch of both."""
+    import numpy as np
+    args = ["--steps", "2", "--warmup", "0", "--size", "64", "--ddpm-steps", "2", "--batch", "3"]
+    dumps = []
+    for k, gpus in enumerate((1, 1, 2)):
+        d = tmp_path / f"run{k}"
+        p = _run(["--gpus", str(gpus)] + args + ["--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert len([l for l in p.stdout.splitlines() if l.startswith("{")]) == 1, p.stdout
+        img, idx = np.load(d / "images.npy"), np.load(d / "images_index.npy")
+        assert img.dtype == np.float32 and idx.dtype == np.float64
+        assert img.shape == (3 * gpus, 64, 64, 3) and idx.tolist() == list(range(3 * gpus))
+        assert img.min() >= 0 and img.max() <= 255 and np.array_equal(img, np.round(img))
+        dumps.append(img)
+    assert np.array_equal(dumps[0], dumps[1])
+    assert np.array_equal(dumps[2][:3], dumps[0]) and not np.array_equal(dumps[2][3:], dumps[0])   # rank 1 draws its own noise
+
+
+def test_dump_outputs_stays_within_64_mb(tmp_path):
+    """64 images of 512x512x3 are 201 MB as float32: a fixed sample of whole images is written, at most 64 MB in all."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        p = _run(["--gpus", "1", "--steps", "1", "--warmup", "0", "--size", "512", "--ddpm-steps", "1", "--batch", "64",
+                  "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        img, idx = np.load(d / "images.npy"), np.load(d / "images_index.npy")
+        assert img.shape == (len(idx), 512, 512, 3) and len(idx) >= 16
+        assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 64
+        runs.append((img, idx))
+    assert np.array_equal(runs[0][1], runs[1][1]) and np.array_equal(runs[0][0], runs[1][0])
+
+
+def test_steps_must_be_positive():
+    p = _run(["--gpus", "1", "--steps", "0", "--warmup", "0", "--size", "64", "--ddpm-steps", "2"])
+    assert p.returncode != 0 and "--steps" in p.stderr
