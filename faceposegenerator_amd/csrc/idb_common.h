@@ -108,6 +108,24 @@ extern unsigned long long idb_launch_counter;   // idb_misc.hip; read through id
         }                                                                          \
     } while (0)
 
+// Launch kernel instance K with `lds` bytes of dynamic LDS.  Before its first launch the instance's dynamic-LDS limit is set to
+// `lds_max` bytes; a failure there is reported as "<api>: hipFuncSetAttribute...", a failed launch as "<name>: launch failed...".
+template <auto K, typename P>
+static int idb_launch(const char* api, const char* name, dim3 grid, dim3 block, size_t lds, int lds_max, hipStream_t st, const P& p) {
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        if (e != hipSuccess) {
+            idb_set_error("%s: hipFuncSetAttribute(%d) failed: %s", api, lds_max, hipGetErrorString(e));
+            return IDB_EHIP;
+        }
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(K, grid, block, lds, st, p);
+    IDB_CHECK_LAUNCH(name);
+    return IDB_OK;
+}
+
 static inline bool idb_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 static inline bool idb_is_operand_dtype(int dt) { return dt == IDB_BF16 || dt == IDB_F16; }
 

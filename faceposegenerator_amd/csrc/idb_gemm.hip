@@ -1648,19 +1648,166 @@ __global__ __launch_bounds__(256, 2) void idb_gemm_kernel_pl(const GemmParams p)
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-struct TileCfg { int mf, nf, wm; };   // tile = (16*mf*wm) x (32*nf), 128*wm threads
-const TileCfg kTiles[] = {{0, 0, 2}, {4, 5, 2}, {4, 4, 2}, {2, 5, 2}, {1, 2, 4}, {4, 1, 2},
-                          {1, 5, 4}, {1, 4, 4}, {2, 5, 4}, {2, 4, 4}};   // index = desc.tile % 10
-// desc.tile = id + 10 * variant.  ids 4 and 6-9 have 8 waves per workgroup (2- or 3-stage ring): 4 = 64x64, 6 = 64x160,
-// 7 = 64x128, 8 = 128x160, 9 = 128x128 — 6-9 are the tiles 3/-/1/2 with half the LDS-DMA instructions per wave and K-step;
-// 4 exists to put more workgroups on the chip for the smallest batch-1 projections (M = 512, N = 1280: 160 instead of 80)
+struct Plan;
+
+// ---- kernel variants ---------------------------------------------------------------------------------
+// A tile id (idb_gemm_desc.tile, idb_gemm_plan's `tile`; include/idb_kernels.h) is shape + 10 * family.
+struct Shape { int mf, nf, wm; };   // tile = (16*mf*wm) x (32*nf), 128*wm MFMA threads
+constexpr Shape kShapes[] = {{0, 0, 2}, {4, 5, 2}, {4, 4, 2}, {2, 5, 2}, {1, 2, 4}, {4, 1, 2},
+                             {1, 5, 4}, {1, 4, 4}, {2, 5, 4}, {2, 4, 4}};   // index = shape
+// shapes 4 and 6-9 have 8 waves per workgroup (2- or 3-stage ring): 4 = 64x64, 6 = 64x160, 7 = 64x128, 8 = 128x160, 9 = 128x128 — 6-9
+// are the tiles 3/-/1/2 with half the LDS-DMA instructions per wave and K-step; 4 exists to put more workgroups on the chip for the
+// smallest batch-1 projections (M = 512, N = 1280: 160 instead of 80)
 // (a 256x160 tile with 8 waves was measured 3-8 % slower than 128x160 with two workgroups per CU and is not kept).
-constexpr int kNumTiles = 9;
+
+enum Family {        // = tile id / 10
+    kRing2,          // 0: LDS-DMA ring (idb_gemm_kernel), 2 stages
+    kRing3,          // 1: 3 stages
+    kRing4,          // 2: 4 stages
+    kRegStaged,      // 3: register-staged double buffer (idb_gemm_kernel_rs)
+    kPersistent,     // 4: persistent, plain [M][K] matrices (idb_gemm_kernel_pl)
+    kLw3x4,          // 5: loader-wave variant (idb_gemm_kernel_lw): 4 loader waves + 3-stage ring
+    kLw3x8,          // 6: 8 loader waves + 3 stages
+    kLw4x4,          // 7: 4 loader waves + 4 stages
+    kLw256,          // 8: loader waves with TWICE the rows (shapes 8 / 9 only: 256x160 / 256x128, 8 MFMA waves + 4 loader waves, 3-stage
+                     //    ring, one workgroup per CU with all 160 KB of LDS): 97 / 85 FLOP per byte moved L2 -> LDS instead of 73 for large grids
+    kPatch256,       // 9: patch-resident 3x3 conv (idb_conv_patch_kernel) on those 256-row tiles
+    kPatchSmall,     // 10: patch-resident 3x3 conv on the shape's own 64- / 128-row tile (fused GroupNorm: transforming patch loaders)
+};
+
+struct Variant;
+using LaunchFn = int (*)(const Variant&, const GemmParams&, const Plan&, hipStream_t);
+
+struct Variant {
+    int id;
+    Family fam;
+    int mf, nf, ns, wm, lw;             // the kernel's template shape (lw: loader waves; the patch kernel's 2 patch + 2 weight loaders)
+    int bm, bn, threads, epi_threads;   // tile, workgroup size, threads of the LDS-staged epilogue (the MFMA waves)
+    int lds;                            // dynamic LDS bytes
+    int gn_lds;                         // fused-GroupNorm twin: its LDS ring (normalizer-wave kernel) / all its LDS (patch kernel); 0: none
+    bool xcd_round;                     // the planner rounds a heuristic split-K to one K-slice per XCD (S % 8 == 0 or S == 4)
+    bool xcd_slices;                    // the kernel runs the K-slice-per-XCD remap (GemmParams.xcd_mode 1 / 2) when the split allows
+    LaunchFn launch[2], launch_gn[2];   // [bf16, f16]; launch_gn: the fused-GroupNorm twin (nullptr: none)
+};
 
 struct Plan {
-    int tile, splitk, tiles_m, tiles_n, ktiles, kt_per_split, M;
+    const Variant* v;
+    int splitk, tiles_m, tiles_n, ktiles, kt_per_split, M;
     long long K;
 };
+
+constexpr int patch_lds(int mf, int nf, int ns, bool gn) {   // two patch buffers + the weight ring (+ group statistics)
+    return 2 * (mf == 1 ? (gn ? 224 : 208) : mf == 2 ? (gn ? 288 : 272) : 400) * 128 + ns * 32 * nf * 128 + (gn ? 256 : 0);
+}
+
+// fused GroupNorm through normalizer waves: LDS = ring + {k, h} table per normalised channel + group statistics, per sample in the tile
+size_t gn_fused_lds(const Variant& v, long long hw, long long cn, int groups) {
+    const long long nsamp = v.bm > hw ? v.bm / hw : 1;
+    return (size_t)v.gn_lds + (size_t)(nsamp * cn * 8) + (size_t)(nsamp * groups * 8);
+}
+
+template <typename T, Family F, int MF, int NF, int NS, int WM, int LW, bool GN>
+int launch_variant(const Variant& v, const GemmParams& p, const Plan& pl, hipStream_t st) {
+    const int tiles = pl.tiles_m * pl.tiles_n;
+    const dim3 grid(tiles, 1, pl.splitk);
+    if constexpr (GN && F == kPatchSmall) {
+        return idb_launch<idb_conv_patch_kernel<T, MF, NF, NS, true>>("idb_gemm", "idb_gemm(patch)", grid, dim3(896), v.gn_lds, v.gn_lds, st, p);
+    } else if constexpr (GN) {
+        // 4 MFMA waves (2 x 2, one per SIMD: the wave tile is twice that of the 8-wave kernels of the same workgroup tile) + 4 loader waves +
+        // 8 normalizer waves = 16 waves: with 4 normalizer waves the transform (9x redundant for a 3x3 conv: every tap re-reads its pixels)
+        // was the K-step's critical path — 50 vs 34 us on conv 320->320 @64x64 at B_eff 2.  64-row tiles only, 4-stage ring: a 4-wave MFMA
+        // role needs > 128 VGPRs on 128-row tiles (16 waves per workgroup)
+        const size_t lds = gn_fused_lds(v, p.HW, p.gn_in_c, p.gn_in_groups);
+        if (lds > 160 * 1024) {
+            idb_set_error("idb_gemm: fused GroupNorm needs %zu bytes of LDS for this tile", lds);
+            return IDB_EUNSUPPORTED;
+        }
+        return idb_launch<idb_gemm_kernel_gn<T, 2, NF, 4, 2, 8>>("idb_gemm", "idb_gemm(gn)", grid, dim3(128 * 2 + 256 + 64 * 8), lds, 160 * 1024, st, p);
+    } else if constexpr (F <= kRing4) {
+        return idb_launch<idb_gemm_kernel<T, MF, NF, NS, WM>>("idb_gemm", "idb_gemm", grid, dim3(v.threads), v.lds, v.lds, st, p);
+    } else if constexpr (F == kRegStaged) {
+        return idb_launch<idb_gemm_kernel_rs<T, MF, NF>>("idb_gemm", "idb_gemm(rs)", grid, dim3(v.threads), v.lds, v.lds, st, p);
+    } else if constexpr (F == kPersistent) {
+        return idb_launch<idb_gemm_kernel_pl<T, MF, NF>>("idb_gemm", "idb_gemm(pl)", dim3(tiles < 512 ? tiles : 512), dim3(v.threads), v.lds, v.lds, st, p);
+    } else if constexpr (F <= kLw256) {
+        return idb_launch<idb_gemm_kernel_lw<T, MF, NF, NS, WM, LW>>("idb_gemm", "idb_gemm(lw)", grid, dim3(v.threads), v.lds, v.lds, st, p);
+    } else {
+        return idb_launch<idb_conv_patch_kernel<T, MF, NF, NS>>("idb_gemm", "idb_gemm(patch)", grid, dim3(v.threads), v.lds, v.lds, st, p);
+    }
+}
+
+template <Family F, int S>
+constexpr Variant variant() {
+    constexpr Shape s = kShapes[S];
+    constexpr int MF = F == kLw256 || F == kPatch256 ? 2 * s.mf : s.mf, NF = s.nf, WM = s.wm;
+    constexpr int NS = F <= kRing4 ? 2 + F : F == kRegStaged || F == kPersistent ? 2 : F == kLw4x4 || F == kPatchSmall ? 4 : 3;
+    constexpr int LW = F == kLw3x8 ? 8 : F >= kLw3x4 ? 4 : 0;
+    constexpr int BM = 16 * MF * WM, BN = 32 * NF;
+    constexpr int RS = F >= kLw3x4 ? 8 * LW : 16 * WM;                      // tile rows per staging sweep (weight rows rounded up to it)
+    constexpr int LDS = F >= kPatch256 ? patch_lds(MF, NF, NS, false) : (BM + (BN + RS - 1) / RS * RS) * 128 * NS;
+    constexpr bool gn = F == kPatchSmall || (F >= kLw3x4 && F <= kLw4x4 && BM == 64);
+    constexpr int GN_LDS = !gn ? 0 : F == kPatchSmall ? patch_lds(MF, NF, NS, true) : (BM + (BN + 31) / 32 * 32) * 128 * 4;
+    static_assert(LDS <= 160 * 1024 && GN_LDS <= 160 * 1024, "LDS does not fit");
+    constexpr bool ring_or_lw = F <= kRing3 || F >= kLw3x4;
+    LaunchFn gn_bf16 = nullptr, gn_f16 = nullptr;
+    if constexpr (gn) {
+        gn_bf16 = launch_variant<__bf16, F, MF, NF, NS, WM, LW, true>;
+        gn_f16 = launch_variant<_Float16, F, MF, NF, NS, WM, LW, true>;
+    }
+    return {S + 10 * F, F, MF, NF, NS, WM, LW, BM, BN, 128 * WM + 64 * LW, 128 * WM, LDS, GN_LDS, ring_or_lw && WM == 4, ring_or_lw && S != 5,
+            {launch_variant<__bf16, F, MF, NF, NS, WM, LW, false>, launch_variant<_Float16, F, MF, NF, NS, WM, LW, false>}, {gn_bf16, gn_f16}};
+}
+
+constexpr Variant kVariants[] = {
+    variant<kRing2, 1>(), variant<kRing2, 2>(), variant<kRing2, 3>(), variant<kRing2, 4>(), variant<kRing2, 5>(),
+    variant<kRing2, 6>(), variant<kRing2, 7>(), variant<kRing2, 8>(), variant<kRing2, 9>(),
+    variant<kRing3, 1>(), variant<kRing3, 2>(), variant<kRing3, 3>(), variant<kRing3, 4>(),
+    variant<kRing3, 6>(), variant<kRing3, 7>(), variant<kRing3, 8>(), variant<kRing3, 9>(),
+    variant<kRing4, 1>(), variant<kRing4, 2>(), variant<kRing4, 3>(),
+    variant<kRegStaged, 1>(), variant<kRegStaged, 2>(), variant<kRegStaged, 3>(), variant<kRegStaged, 5>(),
+    variant<kPersistent, 1>(), variant<kPersistent, 2>(),
+    variant<kLw3x4, 4>(), variant<kLw3x4, 6>(), variant<kLw3x4, 7>(), variant<kLw3x4, 8>(), variant<kLw3x4, 9>(),
+    variant<kLw3x8, 4>(), variant<kLw3x8, 6>(), variant<kLw3x8, 7>(), variant<kLw3x8, 8>(), variant<kLw3x8, 9>(),
+    variant<kLw4x4, 4>(), variant<kLw4x4, 6>(), variant<kLw4x4, 7>(), variant<kLw4x4, 8>(), variant<kLw4x4, 9>(),
+    variant<kLw256, 8>(), variant<kLw256, 9>(),
+    variant<kPatch256, 8>(), variant<kPatch256, 9>(),
+    variant<kPatchSmall, 4>(), variant<kPatchSmall, 6>(), variant<kPatchSmall, 7>(), variant<kPatchSmall, 8>(), variant<kPatchSmall, 9>(),
+};
+
+const Variant* find_variant(int id) {   // nullptr: no such variant
+    for (const Variant& v : kVariants)
+        if (v.id == id) return &v;
+    return nullptr;
+}
+
+// ---- A/B switches for measurements: read once per process ---------------------------------------------
+int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+struct PlanEnv {
+    int plan_ab = env_int("IDB_GEMM_PLAN_AB", 0);                  // bits: 1 keeps 64x128 over 64x64, 2 / 4 move two 128-row thresholds
+    int patch_shortcut = env_int("IDB_CONV_PATCH_SHORTCUT", 0);
+    int ring_small_m = env_int("IDB_GEMM_RING_SMALL_M", 2);
+    int ring_m = env_int("IDB_GEMM_RING_M", 2048);
+    int regstage = env_int("IDB_GEMM_REGSTAGE", 0);
+    int persist = env_int("IDB_GEMM_PERSIST", 1);
+    int pl_geglu_tiles = env_int("IDB_GEMM_PL_GEGLU_TILES", 512);
+    int lw = env_int("IDB_GEMM_LW", 7);
+    int big_tiles = env_int("IDB_GEMM_BIG_TILES", 512);
+    int patch = env_int("IDB_CONV_PATCH", 1);
+    int patch_small = env_int("IDB_CONV_PATCH_SMALL", 0);
+    int xcd_slices = env_int("IDB_GEMM_XCD_SLICES", 1);
+    int pl_ln = env_int("IDB_GEMM_PL_LN", 0);
+    int gn_tapmajor = env_int("IDB_GN_TAPMAJOR", 0);
+    int fused_reduce = env_int("IDB_GEMM_FUSED_REDUCE", 0);
+};
+
+const PlanEnv& plan_env() {
+    static const PlanEnv env;
+    return env;
+}
 
 // idb_conv_patch_kernel's shapes: whole tiles of bm (64 / 128 / 256) output pixels that are whole image rows (or whole images), every
 // K segment on the output grid; the halo patch of one tile fits the kernel's patch buffer (208 / 272 / 400 pixels)
@@ -1684,10 +1831,9 @@ static bool conv_patch_ok(const idb_gemm_desc* d, long long M, int bm) {
     }
     // 1x1 K segments (a fused conv_shortcut) run through the patch buffers with ONE K-step per chunk, i.e. on a two-deep pipeline:
     // auto plans take the patch kernel for pure 3x3 convs only unless IDB_CONV_PATCH_SHORTCUT=1 (forced tile ids run every mix)
-    static const int env_sc = [] { const char* e = getenv("IDB_CONV_PATCH_SHORTCUT"); return e ? atoi(e) : 0; }();
     for (int s = 0; s < d->nsrc; ++s) {
         if (d->src[s].upsample || d->src[s].in_h != H || d->src[s].in_w != W || d->src[s].channels % 64) return false;
-        if (d->src[s].taps != 9 && d->tile == 0 && !env_sc) return false;
+        if (d->src[s].taps != 9 && d->tile == 0 && !plan_env().patch_shortcut) return false;
     }
     return true;
 }
@@ -1745,22 +1891,16 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
     pl->M = (int)M;
     pl->K = K;
     pl->ktiles = (int)(K / 64);
-    int tile = d->tile % 10, ring3 = d->tile / 10;     // ring3: 0 -> 2-stage, 1 -> 3-stage, 2 -> 4-stage LDS ring
-    // ring3: 0 -> 2-stage LDS-DMA ring, 1 -> 3-stage, 2 -> 4-stage, 3 -> register-staged double buffer, 4 -> persistent (plain matrices)
-    // 5 / 6 / 7 -> loader-wave variant (idb_gemm_kernel_lw): 4 loader waves + 3-stage ring / 8 loader waves + 3 stages / 4 loader waves + 4 stages
-    // 8 -> loader-wave variant with TWICE the rows (shapes 8 / 9 only: 256x160 / 256x128, 8 MFMA waves + 4 loader waves, 3-stage ring, one
-    //      workgroup per CU with all 160 KB of LDS): 97 / 85 FLOP per byte moved L2 -> LDS instead of 73 for large grids
-    const bool lw_tile = tile == 4 || (tile >= 6 && tile <= 9);
-    IDB_REQUIRE(d->tile >= 0 && tile <= kNumTiles && ring3 <= 10 && !(ring3 && tile == 0) && !((ring3 == 1 || ring3 == 2) && tile == 5) &&
-                    !(ring3 == 4 && tile > 2) && !(ring3 > 1 && ring3 < 5 && (tile >= 6 || tile == 4)) && !(ring3 >= 5 && !lw_tile) &&
-                    !((ring3 == 8 || ring3 == 9) && tile < 8),
-                "idb_gemm: tile id out of range");
+    const Variant* v = find_variant(d->tile);                // forced tile id; 0: chosen by the rules below
+    IDB_REQUIRE(d->tile == 0 || v, "idb_gemm: tile id out of range");
     const bool plain = d->nsrc == 1 && d->src[0].taps == 1 && d->src[0].in_h == 1 && d->src[0].in_w == 1;
     const bool pl_ok = plain && d->split_k <= 1 && d->out_dtype == d->dtype && (d->geglu ? d->n / 2 : d->n) % 4 == 0 &&
                        d->out_ld % 4 == 0 && M * d->out_ld * 2 < (1LL << 31);
-    IDB_REQUIRE(ring3 != 4 || pl_ok, "idb_gemm: the persistent variant needs one plain [M][K] source, operand-dtype output < 2 GiB, no split-K");
+    IDB_REQUIRE(!v || v->fam != kPersistent || pl_ok, "idb_gemm: the persistent variant needs one plain [M][K] source, operand-dtype output < 2 GiB, no split-K");
+    const PlanEnv& env = plan_env();
     int auto_sk = 0;                                    // split-K chosen together with the tile (0: by the rules below)
-    if (tile == 0) {
+    if (!v) {
+        int tile = 0, fam = kRing2;                     // shape and family of the plan
         const bool n160 = (d->n % 160 == 0) && !d->geglu;
         const int bn = d->n <= 32 ? 32 : (n160 ? 160 : 128);
         const long long blocks_big = ((M + 127) / 128) * ((d->n + bn - 1) / bn);
@@ -1778,14 +1918,13 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
         const bool short_k = pl->ktiles <= 10;
         const bool lin = d->nsrc == 1 && d->src[0].taps == 1;          // a plain linear / 1x1 conv
         bool keep7 = false;                                            // a measured 64x128 plan: not narrowed to 64x64 below
-        static const int plan_ab_early = [] { const char* e = getenv("IDB_GEMM_PLAN_AB"); return e ? atoi(e) : 0; }();
         if (d->n <= 32) tile = 5;
         else if (d->geglu && blocks_big >= 256) tile = pl->ktiles >= 16 ? 2 : 9;   // N = 8C, no split-K: 128-row (persistent form for K >= 1024)
-        else if (blocks_big >= (plan_ab_early & 2 ? 512 : 384)) tile = n160 ? 8 : 9;   // measured at batch 3 (384 workgroups): +6 % over the 64-row tiles; at 256 (batch 2): -1.4 %
+        else if (blocks_big >= (env.plan_ab & 2 ? 512 : 384)) tile = n160 ? 8 : 9;   // measured at batch 3 (384 workgroups): +6 % over the 64-row tiles; at 256 (batch 2): -1.4 %
         // (the 4-wave 128x160 tile reads 9 instead of 14 ds_read_b128 per 20 MFMAs and is 2-5 % faster on every long-K conv with
         //  M >= 32,768 in tools/bench_conv.py at B_eff 128 — end to end it changed nothing: batch 64 15.39 vs 15.32-15.35, batch 8 / 16
         //  -0.3 %; not adopted)
-        else if (!d->geglu && pl->ktiles >= 32 && blocks_big <= (plan_ab_early & 4 ? 255 : 256)) {   // = 256 (batch 2, 64x64 level): 37.7 vs 49.8 us
+        else if (!d->geglu && pl->ktiles >= 32 && blocks_big <= (env.plan_ab & 4 ? 255 : 256)) {   // = 256 (batch 2, 64x64 level): 37.7 vs 49.8 us
             int sk = (int)(256 / blocks_big);
             const int cap = pl->ktiles / 8;
             if (sk > cap) sk = cap;
@@ -1796,7 +1935,7 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
                 // 128-row plan stops at 192, and their slabs are half as many — conv 1280->1280 @8x8 21.7 -> 19.0 us, 2560->1280 26.2 -> 26.0
                 // (tools/bench_conv.py 2); a 64-row tile also lies inside one 8x8 sample, so the GroupNorm in front of it can fuse
                 tile = n160 ? 6 : 7;
-                const long long b64 = 2 * ((d->n + 32 * kTiles[tile].nf - 1) / (32 * kTiles[tile].nf));
+                const long long b64 = 2 * ((d->n + 32 * kShapes[tile].nf - 1) / (32 * kShapes[tile].nf));
                 sk = (int)(256 / b64);
                 if (sk > cap) sk = cap;
                 if (sk > 32) sk = 32;
@@ -1819,89 +1958,76 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
                 if (sk > 32) sk = 32;
                 auto_sk = sk < 1 ? 1 : sk;
             }
-            ring3 = 1;
+            fam = kRing3;
         }
-        else if (short_k && M >= 4096) { tile = (n160 && blocks_big < 256) ? 6 : 9; ring3 = tile == 6; }
+        else if (short_k && M >= 4096) { tile = (n160 && blocks_big < 256) ? 6 : 9; fam = tile == 6 ? kRing3 : kRing2; }
         else if (lin && short_k && M < 4096 && ((M + 127) / 128) * ((d->n + 127) / 128) >= 128 && ((M + 127) / 128) * ((d->n + 127) / 128) <= 256) {
             // QKV at 32x32 (M = 2048, N = 1920, K = 640): 240 workgroups of 128x128 with loader waves instead of 480 of 64x128 two per CU:
             // 13.9 -> 12.5 us (tools/bench_small.py)
             tile = 9;
-            ring3 = 1;
+            fam = kRing3;
         }
         else if (lin && n160 && pl->ktiles >= 16 && M >= 4096 && ((M + 63) / 64) * (d->n / 160) <= 256) {
             // FF-out at 64x64 (M = 8192, N = 320, K = 1280): 256 workgroups of 64x160 with loader waves instead of 384 of 64x128 two per CU:
             // 17.9 -> 14.1 us (tools/bench_small.py)
             tile = 6;
-            ring3 = 1;
+            fam = kRing3;
         }
         else tile = (n160 && pl->ktiles >= 32) ? (M >= 4096 ? 6 : 3) : 7;
-        if (tile == 7 && blocks64 <= 256) ring3 = 1;
-        static const int env_ab = [] { const char* e = getenv("IDB_GEMM_PLAN_AB"); return e ? atoi(e) : 0; }();   // A/B switches for measurements
-        if (tile == 7 && blocks64 <= 160 && !d->geglu && !(env_ab & 1) && !keep7) tile = 4;   // 64x64: twice the workgroups (m=512 n=1280 k=1280: 12.6 -> 9.9 us)
-    }
-    if (d->geglu) IDB_REQUIRE(kTiles[tile].nf % 2 == 0, "idb_gemm: GEGLU needs an even-NF tile");
-    if (d->tile == 0 && tile != 5) {
+        if (tile == 7 && blocks64 <= 256) fam = kRing3;
+        if (tile == 7 && blocks64 <= 160 && !d->geglu && !(env.plan_ab & 1) && !keep7) tile = 4;   // 64x64: twice the workgroups (m=512 n=1280 k=1280: 12.6 -> 9.9 us)
+        const bool lw_shape = tile == 4 || tile >= 6;                  // the 8-wave shapes: loader-wave and 256-row forms exist
         // weight-bound layers stream cold weights from HBM once per launch: a deeper ring keeps more loads in flight
-        static const int env_ring = [] { const char* e = getenv("IDB_GEMM_RING_SMALL_M"); return e ? atoi(e) : 2; }();
-        static const int env_m = [] { const char* e = getenv("IDB_GEMM_RING_M"); return e ? atoi(e) : 2048; }();
-        if (M <= env_m && env_ring >= 3 && env_ring <= 4) ring3 = env_ring - 2;
-    }
-    if (d->tile == 0) {
-        static const int env_rs = [] { const char* e = getenv("IDB_GEMM_REGSTAGE"); return e ? atoi(e) : 0; }();
-        if (env_rs) ring3 = 3;
-        static const int env_pl = [] { const char* e = getenv("IDB_GEMM_PERSIST"); return e ? atoi(e) : 1; }();
-        const long long tiles = ((M + 127) / 128) * ((d->n + (32 * kTiles[tile].nf) - 1) / (32 * kTiles[tile].nf));
+        if (tile != 5 && M <= env.ring_m && env.ring_small_m >= 3 && env.ring_small_m <= 4) fam = env.ring_small_m - 2;
+        if (env.regstage) fam = kRegStaged;
+        const long long tiles = ((M + 127) / 128) * ((d->n + (32 * kShapes[tile].nf) - 1) / (32 * kShapes[tile].nf));
         // measured: +12-15 % on the GEGLU projections (N = 8C, K = C), neutral or slightly negative on the other K = C layers
-        if (env_pl && pl_ok && d->geglu && tile == 2 && pl->ktiles <= 24 && tiles >= 256 && d->split_k <= 1) ring3 = 4;
+        if (env.persist && pl_ok && d->geglu && tile == 2 && pl->ktiles <= 24 && tiles >= 256 && d->split_k <= 1) fam = kPersistent;
         // with the bias vectors loaded at the tile's first K-step (round 2) the persistent form also wins the SHORT-K GEGLU
         // projections once the grid is many rounds deep: K = 320: 593 vs 529 TFLOP/s, K = 640: 795 vs 637 (B_eff = 128,
         // tools/bench_proj.py).  It cannot fold the LayerNorm (ln_stats -> IDB_EUNSUPPORTED, the caller keeps idb_layernorm); end
         // to end with that launch back: batch 64 14.76 -> 15.12, batch 8 13.63 -> 13.87, batch 1 6.44 -> 6.52 images/s
-        static const int env_plg = [] { const char* e = getenv("IDB_GEMM_PL_GEGLU_TILES"); return e ? atoi(e) : 512; }();
-        if (env_pl && pl_ok && d->geglu && tile == 9 && env_plg > 0 && tiles >= env_plg && d->split_k <= 1) { tile = 2; ring3 = 4; }
-    }
-    if (d->tile == 0 && ring3 == 1 && (tile == 4 || (tile >= 6 && tile <= 9))) {
-        // one workgroup per CU (ring-3 plans): loader waves take the DMA issue and the waits off the MFMA waves (idb_gemm_kernel_lw)
-        // measured (tools/bench_lw.py, B_eff 2, cold weights in a HIP graph): conv 320->320 @64x64 31.3 -> 23.7 us, the other convs of the
-        // 64x64 / 32x32 levels -5...-10 %, weight-streaming 16x16 / 8x8 layers and short-K linears 0...-3 %; 4 loader waves with a
-        // 4-stage ring (7) >= 4 with 3 stages (5) >= 8 with 3 stages (6); end to end batch 1 +1.1 %.  IDB_GEMM_LW=0: ring-3 kernels
-        static const int env_lw = [] { const char* e = getenv("IDB_GEMM_LW"); return e ? atoi(e) : 7; }();
-        if (env_lw >= 5 && env_lw <= 7) ring3 = env_lw;
-    }
-    if (d->tile == 0 && ring3 == 0 && (tile == 8 || tile == 9) && !d->geglu && pl->ktiles >= 20) {
-        // large grids, K >= 1280: 256-row loader-wave tiles once the 256-row grid is still >= IDB_GEMM_BIG_TILES workgroups (two rounds of
-        // the chip; 0 = off).  Measured at B_eff 128 (tools/bench_conv.py / bench_proj.py): every 3x3 conv +8...+19 % (1.01-1.17 ->
-        // 1.08-1.32 PFLOP/s), K >= 1280 projections +3...+15 %, K = 640 equal, K = 320 -19 % (excluded); batch 64 end to end +4.1 %
-        static const int env_big = [] { const char* e = getenv("IDB_GEMM_BIG_TILES"); return e ? atoi(e) : 512; }();
-        const long long blocks256 = ((M + 255) / 256) * ((d->n + 32 * kTiles[tile].nf - 1) / (32 * kTiles[tile].nf));
-        if (env_big > 0 && blocks256 >= env_big) ring3 = 8;
-        // 3x3 stride-1 convs on that plan: the patch-resident form (idb_conv_patch_kernel).  IDB_CONV_PATCH=0: tap-major 256-row tiles
-        static const int env_patch = [] { const char* e = getenv("IDB_CONV_PATCH"); return e ? atoi(e) : 1; }();
-        if (ring3 == 8 && env_patch && d->split_k <= 1 && conv_patch_ok(d, M, 256)) ring3 = 9;
-    }
-    if (d->tile == 0 && ring3 >= 5 && ring3 <= 7 && !d->geglu) {
+        if (env.persist && pl_ok && d->geglu && tile == 9 && env.pl_geglu_tiles > 0 && tiles >= env.pl_geglu_tiles && d->split_k <= 1) { tile = 2; fam = kPersistent; }
+        if (fam == kRing3 && lw_shape) {
+            // one workgroup per CU (ring-3 plans): loader waves take the DMA issue and the waits off the MFMA waves (idb_gemm_kernel_lw)
+            // measured (tools/bench_lw.py, B_eff 2, cold weights in a HIP graph): conv 320->320 @64x64 31.3 -> 23.7 us, the other convs of the
+            // 64x64 / 32x32 levels -5...-10 %, weight-streaming 16x16 / 8x8 layers and short-K linears 0...-3 %; 4 loader waves with a
+            // 4-stage ring (7) >= 4 with 3 stages (5) >= 8 with 3 stages (6); end to end batch 1 +1.1 %.  IDB_GEMM_LW=0: ring-3 kernels
+            if (env.lw >= kLw3x4 && env.lw <= kLw4x4) fam = env.lw;
+        }
+        if (fam == kRing2 && (tile == 8 || tile == 9) && !d->geglu && pl->ktiles >= 20) {
+            // large grids, K >= 1280: 256-row loader-wave tiles once the 256-row grid is still >= IDB_GEMM_BIG_TILES workgroups (two rounds of
+            // the chip; 0 = off).  Measured at B_eff 128 (tools/bench_conv.py / bench_proj.py): every 3x3 conv +8...+19 % (1.01-1.17 ->
+            // 1.08-1.32 PFLOP/s), K >= 1280 projections +3...+15 %, K = 640 equal, K = 320 -19 % (excluded); batch 64 end to end +4.1 %
+            const long long blocks256 = ((M + 255) / 256) * ((d->n + 32 * kShapes[tile].nf - 1) / (32 * kShapes[tile].nf));
+            if (env.big_tiles > 0 && blocks256 >= env.big_tiles) fam = kLw256;
+            // 3x3 stride-1 convs on that plan: the patch-resident form (idb_conv_patch_kernel).  IDB_CONV_PATCH=0: tap-major 256-row tiles
+            if (fam == kLw256 && env.patch && d->split_k <= 1 && conv_patch_ok(d, M, 256)) fam = kPatch256;
+        }
         // the same for the one-workgroup-per-CU plans (64- / 128-row tiles, split-K by whole chunks): IDB_CONV_PATCH_SMALL=1
-        static const int env_ps = [] { const char* e = getenv("IDB_CONV_PATCH_SMALL"); return e ? atoi(e) : 0; }();
-        if ((env_ps || d->gn_in_partials) && conv_patch_ok(d, M, 16 * kTiles[tile].mf * kTiles[tile].wm)) ring3 = 10;
+        if (fam >= kLw3x4 && fam <= kLw4x4 && !d->geglu && (env.patch_small || d->gn_in_partials) &&
+            conv_patch_ok(d, M, 16 * kShapes[tile].mf * kShapes[tile].wm))
+            fam = kPatchSmall;
+        v = find_variant(tile + 10 * fam);
+        IDB_REQUIRE(v, "idb_gemm: the A/B switches chose tile %d, which is not built", tile + 10 * fam);
     }
-    if ((ring3 == 9 && !(d->split_k <= 1 && conv_patch_ok(d, M, 256))) || (ring3 == 10 && !conv_patch_ok(d, M, 16 * kTiles[tile].mf * kTiles[tile].wm))) {
+    if (d->geglu) IDB_REQUIRE(v->nf % 2 == 0, "idb_gemm: GEGLU needs an even-NF tile");
+    if ((v->fam == kPatch256 && !(d->split_k <= 1 && conv_patch_ok(d, M, 256))) || (v->fam == kPatchSmall && !conv_patch_ok(d, M, v->bm))) {
         idb_set_error("idb_gemm: tile %d (patch-resident conv) needs a 3x3 stride-1 pad-1 first source, 1x1 / 3x3 sources on the output grid without "
                       "upsampling, out_w in {8,16,32,64}, whole tiles of 256 pixels, no folded LayerNorm / fused GroupNorm / GEGLU / split-K", d->tile);
         return IDB_EUNSUPPORTED;
     }
-    pl->tile = tile + 10 * ring3;
-    const int bm = 16 * kTiles[tile].mf * kTiles[tile].wm * (ring3 == 8 || ring3 == 9 ? 2 : 1), bn = 32 * kTiles[tile].nf;
-    pl->tiles_m = (int)((M + bm - 1) / bm);
-    pl->tiles_n = (d->n + bn - 1) / bn;
+    pl->v = v;
+    pl->tiles_m = (int)((M + v->bm - 1) / v->bm);
+    pl->tiles_n = (d->n + v->bn - 1) / v->bn;
     const long long blocks = (long long)pl->tiles_m * pl->tiles_n;
     IDB_REQUIRE(blocks < (1LL << 31), "idb_gemm: grid too large");
     int sk = d->split_k;
     if (sk <= 0) {
         sk = 1;
-        const bool small_tile = kTiles[tile].mf * kTiles[tile].wm <= 4 && ring3 != 8 && ring3 != 9;     // 64-row tiles
         if (auto_sk) {
             sk = auto_sk;
-        } else if (!d->geglu && small_tile && blocks < 96 && pl->ktiles >= 10) {
+        } else if (!d->geglu && v->bm <= 64 && blocks < 96 && pl->ktiles >= 10) {
             // measured (tools/bench_small.py): with the 3-deep ring a short K loop is cheaper than a split + reduce launch
             // unless the grid is tiny (M = 128)
             sk = (int)((160 + blocks - 1) / blocks);
@@ -1909,7 +2035,7 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
             if (sk > max_by_k) sk = max_by_k;
             if (sk > 32) sk = 32;
             if (sk < 1) sk = 1;
-        } else if (!d->geglu && !small_tile && blocks < 192 && pl->ktiles >= 10) {
+        } else if (!d->geglu && v->bm > 64 && blocks < 192 && pl->ktiles >= 10) {
             sk = (int)((384 + blocks - 1) / blocks);
             const int max_by_k = pl->ktiles / 8;
             if (sk > max_by_k) sk = max_by_k;
@@ -1917,21 +2043,18 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
             if (sk < 1) sk = 1;
         }
     }
-    if (pl->tile / 10 == 4 || pl->tile / 10 == 9) sk = 1;
+    if (v->fam == kPersistent || v->fam == kPatch256) sk = 1;
     IDB_REQUIRE(!(d->geglu && sk > 1), "idb_gemm: GEGLU does not support split-K");
     if (d->act) sk = 1;
     if (sk > pl->ktiles) sk = pl->ktiles;
     if (sk < 1) sk = 1;
-    if (d->split_k <= 0 && !(d->flags & 16) && (pl->tile / 10 <= 1 || pl->tile / 10 >= 5) && kTiles[tile].wm == 4) {
+    if (d->split_k <= 0 && !(d->flags & 16) && v->xcd_round && env.xcd_slices) {
         // one K-slice per XCD (kernel remap modes 1/2) needs S % 8 == 0 or S == 4: round the heuristic's choice
-        static const int env_xcd = [] { const char* e = getenv("IDB_GEMM_XCD_SLICES"); return e ? atoi(e) : 1; }();
-        if (env_xcd) {
-            if (sk > 8) {
-                const int up = ((sk + 7) / 8) * 8;
-                sk = (up <= 32 && up * 6 <= pl->ktiles) ? up : (sk / 8) * 8;
-            } else if (sk >= 5) {
-                sk = (8 * 6 <= pl->ktiles) ? 8 : 4;
-            }
+        if (sk > 8) {
+            const int up = ((sk + 7) / 8) * 8;
+            sk = (up <= 32 && up * 6 <= pl->ktiles) ? up : (sk / 8) * 8;
+        } else if (sk >= 5) {
+            sk = (8 * 6 <= pl->ktiles) ? 8 : 4;
         }
     }
     pl->splitk = sk;
@@ -1939,223 +2062,27 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
     return IDB_OK;
 }
 
-template <typename T, int MF, int NF, int NS, int WM = 2>
-int launch_tile(const GemmParams& p, const Plan& pl, hipStream_t st) {
-    constexpr int RS = 16 * WM, NJ = (32 * NF + RS - 1) / RS;
-    constexpr int LDS = (16 * MF * WM + NJ * RS) * 128 * NS;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&idb_gemm_kernel<T, MF, NF, NS, WM>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            idb_set_error("idb_gemm: hipFuncSetAttribute(%d) failed: %s", LDS, hipGetErrorString(e));
-            return IDB_EHIP;
-        }
-        attr_done = true;
-    }
-    dim3 grid(pl.tiles_m * pl.tiles_n, 1, pl.splitk);
-    hipLaunchKernelGGL((idb_gemm_kernel<T, MF, NF, NS, WM>), grid, dim3(128 * WM), LDS, st, p);
-    IDB_CHECK_LAUNCH("idb_gemm");
-    return IDB_OK;
+// the LDS-staged coalesced epilogue runs (`reduced`: the launch writes final outputs, not split-K slabs)
+static bool lds_epilogue_runs(const idb_gemm_desc* d, const Variant& v, bool reduced) {
+    const int no = d->geglu ? d->n / 2 : d->n;
+    return v.fam != kPersistent && d->out_dtype == d->dtype && reduced && no % 8 == 0 && d->out_ld % 8 == 0 && !(d->flags & 4) &&
+           (!d->residual || idb_aligned16(d->residual));
 }
 
-template <typename T, int MF, int NF, int NS, int WM, int LW>
-int launch_tile_lw(const GemmParams& p, const Plan& pl, hipStream_t st) {
-    constexpr int LR = 8 * LW, NJ = (32 * NF + LR - 1) / LR;
-    constexpr int LDS = (16 * MF * WM + NJ * LR) * 128 * NS;
-    static_assert(LDS <= 160 * 1024, "LDS ring does not fit");
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&idb_gemm_kernel_lw<T, MF, NF, NS, WM, LW>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            idb_set_error("idb_gemm: hipFuncSetAttribute(%d) failed: %s", LDS, hipGetErrorString(e));
-            return IDB_EHIP;
-        }
-        attr_done = true;
-    }
-    dim3 grid(pl.tiles_m * pl.tiles_n, 1, pl.splitk);
-    hipLaunchKernelGGL((idb_gemm_kernel_lw<T, MF, NF, NS, WM, LW>), grid, dim3(128 * WM + 64 * LW), LDS, st, p);
-    IDB_CHECK_LAUNCH("idb_gemm(lw)");
-    return IDB_OK;
-}
-
-template <typename T, int MF, int NF, int NS, bool GN = false>
-int launch_conv_patch(const GemmParams& p, const Plan& pl, hipStream_t st) {
-    constexpr int LDS = 2 * (MF == 1 ? (GN ? 224 : 208) : MF == 2 ? (GN ? 288 : 272) : 400) * 128 + NS * 32 * NF * 128 + (GN ? 256 : 0);
-    static_assert(LDS <= 160 * 1024, "patch buffers + weight ring do not fit");
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&idb_conv_patch_kernel<T, MF, NF, NS, GN>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            idb_set_error("idb_gemm: hipFuncSetAttribute(%d) failed: %s", LDS, hipGetErrorString(e));
-            return IDB_EHIP;
-        }
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((idb_conv_patch_kernel<T, MF, NF, NS, GN>), dim3(pl.tiles_m * pl.tiles_n, 1, pl.splitk), dim3(GN ? 896 : 768), LDS, st, p);
-    IDB_CHECK_LAUNCH("idb_gemm(patch)");
-    return IDB_OK;
-}
-
-// fused GroupNorm: LDS = ring + {k, h} table + group statistics; 0 if the shape cannot run (caller: IDB_EUNSUPPORTED)
-static size_t gn_fused_lds(int bm, int stage_rows, int ns, const GemmParams& p) {
-    const int nsamp = bm > p.HW ? bm / p.HW : 1;
-    return (size_t)stage_rows * 128 * ns + (size_t)nsamp * p.gn_in_c * 8 + (size_t)nsamp * p.gn_in_groups * 8;
-}
-
-template <typename T, int MF, int NF, int NS, int WM>
-int launch_tile_gn(const GemmParams& p, const Plan& pl, hipStream_t st) {
-    constexpr int NV = 8, LR = 32, NJ = (32 * NF + LR - 1) / LR, BM = 16 * MF * WM;
-    const size_t lds = gn_fused_lds(BM, BM + NJ * LR, NS, p);
-    if (lds > 160 * 1024) {
-        idb_set_error("idb_gemm: fused GroupNorm needs %zu bytes of LDS for this tile", lds);
-        return IDB_EUNSUPPORTED;
-    }
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&idb_gemm_kernel_gn<T, MF, NF, NS, WM, NV>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            idb_set_error("idb_gemm: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return IDB_EHIP;
-        }
-        attr_lds = 160 * 1024;
-    }
-    dim3 grid(pl.tiles_m * pl.tiles_n, 1, pl.splitk);
-    hipLaunchKernelGGL((idb_gemm_kernel_gn<T, MF, NF, NS, WM, NV>), grid, dim3(128 * WM + 256 + 64 * NV), lds, st, p);
-    IDB_CHECK_LAUNCH("idb_gemm(gn)");
-    return IDB_OK;
-}
-
-template <typename T>
-int launch_gn_by_tile(const GemmParams& p, const Plan& pl, hipStream_t st) {
-    // 4 MFMA waves (2 x 2, one per SIMD: the wave tile is twice that of the 8-wave kernels of the same workgroup tile) + 4 loader waves +
-    // 8 normalizer waves = 16 waves: with 4 normalizer waves the transform (9x redundant for a 3x3 conv: every tap re-reads its pixels)
-    // was the K-step's critical path — 50 vs 34 us on conv 320->320 @64x64 at B_eff 2.  64-row tiles: 4-stage ring; 128-row: 3 (LDS)
-    switch (pl.tile % 10) {
-        case 4: return launch_tile_gn<T, 2, 2, 4, 2>(p, pl, st);
-        case 6: return launch_tile_gn<T, 2, 5, 4, 2>(p, pl, st);
-        case 7: return launch_tile_gn<T, 2, 4, 4, 2>(p, pl, st);
-        default:       // 128-row tiles: a 4-wave MFMA role needs > 128 VGPRs there (16 waves per workgroup): not instantiated, gemm_fuses_gn says no
-            idb_set_error("idb_gemm: fused GroupNorm is built for 64-row tiles only");
-            return IDB_EUNSUPPORTED;
-    }
-}
-
-template <typename T, int NS, int LW>
-int launch_lw_by_tile(const GemmParams& p, const Plan& pl, hipStream_t st) {
-    switch (pl.tile % 10) {
-        case 4: return launch_tile_lw<T, 1, 2, NS, 4, LW>(p, pl, st);
-        case 6: return launch_tile_lw<T, 1, 5, NS, 4, LW>(p, pl, st);
-        case 7: return launch_tile_lw<T, 1, 4, NS, 4, LW>(p, pl, st);
-        case 8: return launch_tile_lw<T, 2, 5, NS, 4, LW>(p, pl, st);
-        default: return launch_tile_lw<T, 2, 4, NS, 4, LW>(p, pl, st);
-    }
-}
-
-template <typename T, int MF, int NF>
-int launch_tile_rs(const GemmParams& p, const Plan& pl, hipStream_t st) {
-    constexpr int LDS = (32 * MF + 32 * NF) * 128 * 2;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&idb_gemm_kernel_rs<T, MF, NF>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            idb_set_error("idb_gemm: hipFuncSetAttribute(%d) failed: %s", LDS, hipGetErrorString(e));
-            return IDB_EHIP;
-        }
-        attr_done = true;
-    }
-    dim3 grid(pl.tiles_m * pl.tiles_n, 1, pl.splitk);
-    hipLaunchKernelGGL((idb_gemm_kernel_rs<T, MF, NF>), grid, dim3(256), LDS, st, p);
-    IDB_CHECK_LAUNCH("idb_gemm(rs)");
-    return IDB_OK;
-}
-
-template <typename T, int MF, int NF>
-int launch_tile_pl(const GemmParams& p, const Plan& pl, hipStream_t st) {
-    constexpr int LDS = (32 * MF + 32 * NF) * 128 * 2;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&idb_gemm_kernel_pl<T, MF, NF>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            idb_set_error("idb_gemm: hipFuncSetAttribute(%d) failed: %s", LDS, hipGetErrorString(e));
-            return IDB_EHIP;
-        }
-        attr_done = true;
-    }
-    const int tiles = pl.tiles_m * pl.tiles_n;
-    hipLaunchKernelGGL((idb_gemm_kernel_pl<T, MF, NF>), dim3(tiles < 512 ? tiles : 512), dim3(256), LDS, st, p);
-    IDB_CHECK_LAUNCH("idb_gemm(pl)");
-    return IDB_OK;
+// ... and can emit row statistics / fold a LayerNorm (not the register-staged kernel's)
+static bool gemm_uses_lds_epilogue(const idb_gemm_desc* d, const Plan& pl) {
+    return pl.v->fam != kRegStaged && lds_epilogue_runs(d, *pl.v, pl.splitk == 1);
 }
 
 template <typename T>
 int launch_all(const idb_gemm_desc* d, const GemmParams& p, const Plan& pl, hipStream_t st) {
-    int rc;
-    if (p.gn_in_part) {
-        if (pl.tile / 10 == 10) {                              // the patch-resident conv with transforming patch loaders
-            switch (pl.tile % 10) {
-                case 4: rc = launch_conv_patch<T, 1, 2, 4, true>(p, pl, st); break;
-                case 6: rc = launch_conv_patch<T, 1, 5, 4, true>(p, pl, st); break;
-                case 7: rc = launch_conv_patch<T, 1, 4, 4, true>(p, pl, st); break;
-                case 8: rc = launch_conv_patch<T, 2, 5, 4, true>(p, pl, st); break;
-                default: rc = launch_conv_patch<T, 2, 4, 4, true>(p, pl, st); break;
-            }
-        } else
-            rc = launch_gn_by_tile<T>(p, pl, st);
-        if (rc != IDB_OK || (d->flags & 1)) return rc;
-        return idb_finish_splitk<T>(p, pl.M, d->n, d->batch, pl.splitk, d->gn_partials, d->gn_groups, d->dtype, st);
+    constexpr int dt = std::is_same<T, __bf16>::value ? 0 : 1;
+    const LaunchFn launch = p.gn_in_part ? pl.v->launch_gn[dt] : pl.v->launch[dt];
+    if (!launch) {
+        idb_set_error("idb_gemm: fused GroupNorm is built for 64-row tiles only");
+        return IDB_EUNSUPPORTED;
     }
-    if (pl.tile / 10 >= 5) {
-        if (pl.tile / 10 == 10) {
-            switch (pl.tile % 10) {
-                case 4: rc = launch_conv_patch<T, 1, 2, 4>(p, pl, st); break;
-                case 6: rc = launch_conv_patch<T, 1, 5, 4>(p, pl, st); break;
-                case 7: rc = launch_conv_patch<T, 1, 4, 4>(p, pl, st); break;
-                case 8: rc = launch_conv_patch<T, 2, 5, 4>(p, pl, st); break;
-                default: rc = launch_conv_patch<T, 2, 4, 4>(p, pl, st); break;
-            }
-        } else if (pl.tile / 10 == 9)
-            rc = pl.tile % 10 == 8 ? launch_conv_patch<T, 4, 5, 3>(p, pl, st) : launch_conv_patch<T, 4, 4, 3>(p, pl, st);
-        else if (pl.tile / 10 == 8)
-            rc = pl.tile % 10 == 8 ? launch_tile_lw<T, 4, 5, 3, 4, 4>(p, pl, st) : launch_tile_lw<T, 4, 4, 3, 4, 4>(p, pl, st);
-        else
-            rc = pl.tile / 10 == 5 ? launch_lw_by_tile<T, 3, 4>(p, pl, st) : pl.tile / 10 == 6 ? launch_lw_by_tile<T, 3, 8>(p, pl, st)
-                                                                                               : launch_lw_by_tile<T, 4, 4>(p, pl, st);
-        if (rc != IDB_OK || (d->flags & 1)) return rc;
-        return idb_finish_splitk<T>(p, pl.M, d->n, d->batch, pl.splitk, d->gn_partials, d->gn_groups, d->dtype, st);
-    }
-    switch (pl.tile) {
-        case 1: rc = launch_tile<T, 4, 5, 2>(p, pl, st); break;
-        case 2: rc = launch_tile<T, 4, 4, 2>(p, pl, st); break;
-        case 3: rc = launch_tile<T, 2, 5, 2>(p, pl, st); break;
-        case 4: rc = launch_tile<T, 1, 2, 2, 4>(p, pl, st); break;
-        case 11: rc = launch_tile<T, 4, 5, 3>(p, pl, st); break;
-        case 12: rc = launch_tile<T, 4, 4, 3>(p, pl, st); break;
-        case 13: rc = launch_tile<T, 2, 5, 3>(p, pl, st); break;
-        case 14: rc = launch_tile<T, 1, 2, 3, 4>(p, pl, st); break;
-        case 6: rc = launch_tile<T, 1, 5, 2, 4>(p, pl, st); break;
-        case 7: rc = launch_tile<T, 1, 4, 2, 4>(p, pl, st); break;
-        case 8: rc = launch_tile<T, 2, 5, 2, 4>(p, pl, st); break;
-        case 16: rc = launch_tile<T, 1, 5, 3, 4>(p, pl, st); break;
-        case 18: rc = launch_tile<T, 2, 5, 3, 4>(p, pl, st); break;
-        case 17: rc = launch_tile<T, 1, 4, 3, 4>(p, pl, st); break;
-        case 19: rc = launch_tile<T, 2, 4, 3, 4>(p, pl, st); break;
-        case 9: rc = launch_tile<T, 2, 4, 2, 4>(p, pl, st); break;
-        case 41: rc = launch_tile_pl<T, 4, 5>(p, pl, st); break;
-        case 42: rc = launch_tile_pl<T, 4, 4>(p, pl, st); break;
-        case 31: rc = launch_tile_rs<T, 4, 5>(p, pl, st); break;
-        case 32: rc = launch_tile_rs<T, 4, 4>(p, pl, st); break;
-        case 33: rc = launch_tile_rs<T, 2, 5>(p, pl, st); break;
-        case 35: rc = launch_tile_rs<T, 4, 1>(p, pl, st); break;
-        case 21: rc = launch_tile<T, 4, 5, 4>(p, pl, st); break;
-        case 22: rc = launch_tile<T, 4, 4, 4>(p, pl, st); break;
-        case 23: rc = launch_tile<T, 2, 5, 4>(p, pl, st); break;
-        default: rc = launch_tile<T, 4, 1, 2>(p, pl, st); break;
-    }
+    const int rc = launch(*pl.v, p, pl, st);
     if (rc != IDB_OK || (d->flags & 1)) return rc;
     return idb_finish_splitk<T>(p, pl.M, d->n, d->batch, pl.splitk, d->gn_partials, d->gn_groups, d->dtype, st);
 }
@@ -2168,13 +2095,6 @@ extern "C" size_t idb_gemm_workspace_bytes(const idb_gemm_desc* d) {
     return pl.splitk > 1 ? (size_t)pl.splitk * pl.M * d->n * sizeof(float) : 0;
 }
 
-// the LDS-staged coalesced epilogue runs for this (descriptor, plan): the only epilogue that emits row statistics / folds a LayerNorm
-static bool gemm_uses_lds_epilogue(const idb_gemm_desc* d, const Plan& pl) {
-    const int no = d->geglu ? d->n / 2 : d->n;
-    return pl.tile / 10 != 4 && pl.tile / 10 != 3 && d->out_dtype == d->dtype && pl.splitk == 1 && no % 8 == 0 && d->out_ld % 8 == 0 && !(d->flags & 4) &&
-           (!d->residual || idb_aligned16(d->residual));
-}
-
 // a folded LayerNorm needs the LDS-staged epilogue, or the persistent variant with >= 2 K-steps (statistics loaded at the first,
 // reduced at the second)
 static bool gemm_folds_ln(const idb_gemm_desc* d, const Plan& pl) {
@@ -2182,17 +2102,15 @@ static bool gemm_folds_ln(const idb_gemm_desc* d, const Plan& pl) {
     // persistent variant: built and tested, but off unless asked for (flags bit 8 / IDB_GEMM_PL_LN=1) — measured on one box, the
     // producer's statistics pass + the fold cost what the idb_layernorm launch costs: batch 64 14.77 -> 14.65 images/s (twice),
     // batch 1 6.645 vs 6.641 with 15 fewer launches
-    static const int env_pl_ln = [] { const char* e = getenv("IDB_GEMM_PL_LN"); return e ? atoi(e) : 0; }();
-    if (pl.tile / 10 == 4) return (env_pl_ln || (d->flags & 256)) && pl.ktiles >= 2;
+    if (pl.v->fam == kPersistent) return (plan_env().pl_ln || (d->flags & 256)) && pl.ktiles >= 2;
     return gemm_uses_lds_epilogue(d, pl);
 }
 
 // the GEMM's own LDS-staged epilogue can emit the first GroupNorm pass of the output (no split-K, whole groups per column tile)
 static bool gemm_epilogue_emits_gn(const idb_gemm_desc* d, const Plan& pl, int groups) {
-    if ((pl.tile / 10 > 2 && pl.tile / 10 < 5) || d->geglu || !gemm_uses_lds_epilogue(d, pl)) return false;
-    const TileCfg& t = kTiles[pl.tile % 10];
-    const int epi_threads = d->gn_in_partials ? 256 : 128 * t.wm;      // the fused-GroupNorm kernel has 4 MFMA waves
-    return idb_epilogue_emits_gn(16 * t.mf * t.wm * (pl.tile / 10 == 8 || pl.tile / 10 == 9 ? 2 : 1), 32 * t.nf, epi_threads, pl.M, d->n, groups) && (long long)d->out_h * d->out_w % 64 == 0 &&
+    if (d->geglu || !gemm_uses_lds_epilogue(d, pl)) return false;
+    const int epi_threads = d->gn_in_partials ? 256 : pl.v->epi_threads;      // the fused-GroupNorm kernel has 4 MFMA waves
+    return idb_epilogue_emits_gn(pl.v->bm, pl.v->bn, epi_threads, pl.M, d->n, groups) && (long long)d->out_h * d->out_w % 64 == 0 &&
            d->out_ld == d->n;
 }
 
@@ -2203,30 +2121,26 @@ extern "C" int32_t idb_gemm_emits_gn_partials(const idb_gemm_desc* d, int32_t gr
     return gemm_epilogue_emits_gn(d, pl, groups) ? 2 : 0;
 }
 
-// the fused GroupNorm runs on the one-workgroup-per-CU loader-wave plans only (variants 5-7), stride 1, every normalised source on
-// the output grid, tiles inside one sample or covering whole samples, no folded LayerNorm on the same launch
+// the fused GroupNorm runs on the patch-resident small tiles, or on the one-workgroup-per-CU loader-wave plans with a normalizer-wave
+// twin (64-row tiles of families 5-7): stride 1, every normalised source on the output grid, tiles inside one sample or covering whole
+// samples, no folded LayerNorm on the same launch
 static bool gemm_fuses_gn(const idb_gemm_desc* d, const Plan& pl) {
+    const Variant& v = *pl.v;
     if (!d->gn_in_partials) return false;
-    if (pl.tile / 10 == 10) return conv_patch_ok(d, pl.M, 16 * kTiles[pl.tile % 10].mf * kTiles[pl.tile % 10].wm);
+    if (v.fam == kPatchSmall) return conv_patch_ok(d, pl.M, v.bm);
     // the tap-major normalizer-wave kernel loses on every 3x3 conv (it re-normalises each pixel per tap): auto plans use it for 1x1 sources
     // only (Transformer2DModel norm + proj_in); forced tile ids and IDB_GN_TAPMAJOR=1 still reach it for 3x3 sources
-    static const int env_tm = [] { const char* e = getenv("IDB_GN_TAPMAJOR"); return e ? atoi(e) : 0; }();
-    if (d->src[0].taps == 9 && d->tile == 0 && !env_tm) return false;
-    if (pl.tile / 10 < 5 || pl.tile / 10 > 7 || d->stride != 1 || d->ln_stats || d->geglu || d->gn_in_nsrc < 1 || d->gn_in_nsrc > d->nsrc) return false;
-    const int bm = 16 * kTiles[pl.tile % 10].mf * kTiles[pl.tile % 10].wm;
-    if (bm != 64) return false;                        // 64x160 / 64x128 / 64x64 plans (launch_gn_by_tile)
+    if (d->src[0].taps == 9 && d->tile == 0 && !plan_env().gn_tapmajor) return false;
+    if (!v.launch_gn[0] || d->stride != 1 || d->ln_stats || d->geglu || d->gn_in_nsrc < 1 || d->gn_in_nsrc > d->nsrc) return false;
     const long long hw = (long long)d->out_h * d->out_w;
-    if (!(hw % bm == 0 || (bm % hw == 0 && bm / hw <= 2))) return false;
+    if (!(hw % v.bm == 0 || (v.bm % hw == 0 && v.bm / hw <= 2))) return false;
     long long cn = 0;
     for (int s = 0; s < d->gn_in_nsrc; ++s) {
         if (d->src[s].upsample || d->src[s].in_h != d->out_h || d->src[s].in_w != d->out_w) return false;
         cn += d->src[s].channels;
     }
     if (d->gn_in_groups <= 0 || cn % d->gn_in_groups || cn / d->gn_in_groups < 1 || d->gn_in_chunks < 1 || d->gn_in_chunks > 64) return false;
-    const int nsamp = bm > hw ? (int)(bm / hw) : 1;
-    const int stage_rows = bm + (32 * kTiles[pl.tile % 10].nf + 31) / 32 * 32;
-    const size_t lds = (size_t)stage_rows * 128 * (bm == 64 ? 4 : 3) + (size_t)nsamp * cn * 8 + (size_t)nsamp * d->gn_in_groups * 8;
-    return lds <= 160 * 1024;
+    return gn_fused_lds(v, hw, cn, d->gn_in_groups) <= 160 * 1024;
 }
 
 extern "C" int32_t idb_gemm_fuses_groupnorm(const idb_gemm_desc* d) {
@@ -2249,12 +2163,11 @@ extern "C" int idb_gemm_plan(const idb_gemm_desc* d, int32_t* tile, int32_t* spl
     Plan pl;
     int rc = plan_gemm(d, &pl);
     if (rc != IDB_OK) return rc;
-    if (tile) *tile = pl.tile;
+    if (tile) *tile = pl.v->id;
     if (split_k) *split_k = pl.splitk;
     if (blocks) *blocks = pl.tiles_m * pl.tiles_n * pl.splitk;
     return IDB_OK;
 }
-
 extern "C" int idb_gemm(const idb_gemm_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
     Plan pl;
     int rc = plan_gemm(d, &pl);
@@ -2287,15 +2200,10 @@ extern "C" int idb_gemm(const idb_gemm_desc* d, void* workspace, size_t workspac
     }
     p.ktiles = pl.ktiles;
     p.kt_per_split = pl.kt_per_split;
-    {
-        // K-slice-per-XCD remap: the 8-wave ring kernels only (the register-staged and persistent variants keep mode 0)
-        static const int env_xcd = [] { const char* e = getenv("IDB_GEMM_XCD_SLICES"); return e ? atoi(e) : 1; }();
-        const long long X = (long long)pl.tiles_m * pl.tiles_n;
-        p.xcd_mode = 0;
-        if (env_xcd && (pl.tile / 10 <= 1 || pl.tile / 10 >= 5) && pl.tile % 10 != 5 && pl.tile % 10 != 0) {
-            if (pl.splitk >= 8 && pl.splitk % 8 == 0) p.xcd_mode = 1;
-            else if (pl.splitk == 4 && X % 2 == 0) p.xcd_mode = 2;
-        }
+    p.xcd_mode = 0;
+    if (plan_env().xcd_slices && pl.v->xcd_slices) {
+        if (pl.splitk >= 8 && pl.splitk % 8 == 0) p.xcd_mode = 1;
+        else if (pl.splitk == 4 && ((long long)pl.tiles_m * pl.tiles_n) % 2 == 0) p.xcd_mode = 2;
     }
     p.splitk = pl.splitk;
     p.w = (const char*)d->w;
@@ -2318,21 +2226,19 @@ extern "C" int idb_gemm(const idb_gemm_desc* d, void* workspace, size_t workspac
     p.act = d->act;
     p.dbg_loop = (d->flags & 64) ? 1 : ((d->flags & 128) ? 2 : 0);
     {
-        const int no = d->geglu ? d->n / 2 : d->n;
         // In-kernel split-K reduce (flags bit 4 only).  Measured on MI355X it LOSES to the separate reduce launch in the
         // sampling loop (batch 1: 4.49 vs 5.11 images/s): every split workgroup pays an agent-scope release (buffer_wbl2
         // of its XCD's L2) and one workgroup per tile re-reads all slabs — the "splitk-seam" price of the CDNA guide.
         // The path is kept, tested bit-identical to the two-launch form, for shapes where a launch boundary is dearer.
-        static const int env_fused = [] { const char* e = getenv("IDB_GEMM_FUSED_REDUCE"); return e ? atoi(e) : 0; }();
+        const int env_fused = plan_env().fused_reduce;
         const bool want_fused = (d->flags & 16) || (env_fused > 0 && pl.splitk <= env_fused);
         const bool fused_reduce = pl.splitk > 1 && d->counters && want_fused && !(d->flags & 8) && !(d->flags & 1) &&
                                   (long long)pl.tiles_m * pl.tiles_n <= d->counters_len;
         p.counters = fused_reduce ? d->counters : nullptr;
-        p.lds_epi = (pl.tile / 10 != 4 && !p.out_f32 && (pl.splitk == 1 || fused_reduce) && no % 8 == 0 && d->out_ld % 8 == 0 && !(d->flags & 4) &&
-                     (!d->residual || idb_aligned16(d->residual))) ? 1 : 0;
+        p.lds_epi = lds_epilogue_runs(d, *pl.v, pl.splitk == 1 || fused_reduce) ? 1 : 0;
     }
     if (d->row_stats_out || d->ln_stats) {
-        if ((d->row_stats_out && (!p.lds_epi || pl.tile / 10 == 3)) || (d->ln_stats && !gemm_folds_ln(d, pl))) {
+        if ((d->row_stats_out && (!p.lds_epi || pl.v->fam == kRegStaged)) || (d->ln_stats && !gemm_folds_ln(d, pl))) {
             idb_set_error("idb_gemm: row_stats_out needs a plan with the LDS-staged epilogue (no split-K, no persistent / register-staged variant); "
                           "ln_stats that or the persistent variant");
             return IDB_EUNSUPPORTED;
@@ -2369,12 +2275,11 @@ extern "C" int idb_gemm(const idb_gemm_desc* d, void* workspace, size_t workspac
     p.w_group_rows = d->w_group_rows;
     p.w_group_stride = d->w_group_stride;
     if (p.w_groups > 1) {
-        const int bm_t = 16 * kTiles[pl.tile % 10].mf * kTiles[pl.tile % 10].wm * (pl.tile / 10 == 8 || pl.tile / 10 == 9 ? 2 : 1);
         IDB_REQUIRE(d->w_group_rows > 0 && d->w_group_stride >= (long long)p.w_bytes && d->w_group_stride % 16 == 0 &&
                         (long long)d->w_groups * d->w_group_stride < (1LL << 40), "idb_gemm: w_groups needs w_group_rows > 0 and a 16-byte-multiple w_group_stride >= one matrix");
-        if (pl.tile / 10 == 4 || d->w_group_rows % bm_t != 0) {
+        if (pl.v->fam == kPersistent || d->w_group_rows % pl.v->bm != 0) {
             idb_set_error("idb_gemm: w_group_rows = %d is not a multiple of the plan's tile height %d (or the persistent variant was chosen): run one launch per group",
-                          d->w_group_rows, bm_t);
+                          d->w_group_rows, pl.v->bm);
             return IDB_EUNSUPPORTED;
         }
     }

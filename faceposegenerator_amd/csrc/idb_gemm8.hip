@@ -374,18 +374,7 @@ template <typename T, int MF, int NF, int NS>
 int launch_gemm8(const Gemm8Params& p, int tiles, hipStream_t st) {
     constexpr int NJ = (32 * NF + 63) / 64;
     constexpr int LDS = (16 * MF * 4 + NJ * 64) * 128 * NS;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&idb_gemm8_kernel<T, MF, NF, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            idb_set_error("idb_gemm_fp8: hipFuncSetAttribute(%d) failed: %s", LDS, hipGetErrorString(e));
-            return IDB_EHIP;
-        }
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((idb_gemm8_kernel<T, MF, NF, NS>), dim3(tiles), dim3(512), LDS, st, p);
-    IDB_CHECK_LAUNCH("idb_gemm_fp8");
-    return IDB_OK;
+    return idb_launch<idb_gemm8_kernel<T, MF, NF, NS>>("idb_gemm_fp8", "idb_gemm_fp8", dim3(tiles), dim3(512), LDS, LDS, st, p);
 }
 
 template <typename T, int MF, int NF, int NS, int LW>
@@ -393,18 +382,7 @@ int launch_gemm8_lw(const Gemm8Params& p, int tiles, hipStream_t st) {
     constexpr int LR = 8 * LW, NJ = (32 * NF + LR - 1) / LR;
     constexpr int LDS = (16 * MF * 4 + NJ * LR) * 128 * NS;
     static_assert(LDS <= 160 * 1024, "LDS ring does not fit");
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&idb_gemm8_kernel_lw<T, MF, NF, NS, LW>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            idb_set_error("idb_gemm_fp8: hipFuncSetAttribute(%d) failed: %s", LDS, hipGetErrorString(e));
-            return IDB_EHIP;
-        }
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((idb_gemm8_kernel_lw<T, MF, NF, NS, LW>), dim3(tiles), dim3(512 + 64 * LW), LDS, st, p);
-    IDB_CHECK_LAUNCH("idb_gemm_fp8(lw)");
-    return IDB_OK;
+    return idb_launch<idb_gemm8_kernel_lw<T, MF, NF, NS, LW>>("idb_gemm_fp8", "idb_gemm_fp8(lw)", dim3(tiles), dim3(512 + 64 * LW), LDS, LDS, st, p);
 }
 
 }  // namespace
