@@ -28,6 +28,7 @@ EXPORTS = [
     "idb_nhwc_to_nchw_f32", "idb_f32_nhwc_to_nchw", "idb_cast_f32", "idb_vae_sample", "idb_warp_affine_u8",
     "idb_crop_resize_area_u8", "idb_conv2d_f32", "idb_maxpool2d_f32", "idb_softmax_pairs_f32", "idb_nms_mask",
     "idb_quantize_fp8", "idb_pack_weight_fp8", "idb_gemm_fp8", "idb_groupnorm_fp8",
+    "idb_arcface_stem", "idb_arcface_head_workspace_bytes", "idb_arcface_head",
 ]
 
 
@@ -49,7 +50,8 @@ class GemmDesc(C.Structure):
                 ("ln_v", C.c_void_p), ("ln_eps", C.c_float), ("pad_mode", C.c_int32), ("w_layout", C.c_int32),
                 ("w_groups", C.c_int32), ("w_group_rows", C.c_int32), ("w_group_stride", C.c_int64),
                 ("gn_in_partials", C.c_void_p), ("gn_in_chunks", C.c_int32), ("gn_in_groups", C.c_int32), ("gn_in_nsrc", C.c_int32),
-                ("gn_in_silu", C.c_int32), ("gn_in_eps", C.c_float), ("gn_in_gamma", C.c_void_p), ("gn_in_beta", C.c_void_p)]
+                ("gn_in_silu", C.c_int32), ("gn_in_eps", C.c_float), ("gn_in_gamma", C.c_void_p), ("gn_in_beta", C.c_void_p),
+                ("act_slope", C.c_void_p), ("out2", C.c_void_p), ("out2_scale", C.c_void_p), ("out2_shift", C.c_void_p)]
 
 
 class GemmFp8Desc(C.Structure):
@@ -126,6 +128,9 @@ def load() -> C.CDLL:
         "idb_pack_weight_fp8": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
         "idb_gemm_fp8": (C.c_int, [C.POINTER(GemmFp8Desc), vp]),
         "idb_groupnorm_fp8": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, f32, i32, vp, sz, vp, i32, vp]),
+        "idb_arcface_stem": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+        "idb_arcface_head_workspace_bytes": (sz, [i32, i32, i32]),
+        "idb_arcface_head": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

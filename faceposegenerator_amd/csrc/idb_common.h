@@ -53,6 +53,13 @@ template <> struct Op<_Float16> {
 
 template <typename T> __device__ __forceinline__ float to_f32(T x) { return (float)x; }
 template <typename T> __device__ __forceinline__ T from_f32(float x) { return (T)x; }
+// fma(x, s, b) rounded to fp32, THEN converted: the empty asm keeps the compiler from fusing the two into v_fma_mix*_f16 (one rounding
+// straight to f16), so f16 and bf16 second outputs share one definition that the host can reproduce
+template <typename T> __device__ __forceinline__ T affine_round(float x, float s, float b) {
+    float r = __builtin_fmaf(x, s, b);
+    asm volatile("" : "+v"(r));
+    return from_f32<T>(r);
+}
 
 // x * sigmoid(x) with v_rcp_f32 (1 ulp) instead of the IEEE division sequence (v_div_scale / v_rcp / 4 FMAs / v_div_fmas / v_div_fixup,
 // ~10 VALU instructions per element): the GroupNorm+SiLU pass at batch 64 is VALU-co-bound, its result is rounded to 16 bits anyway

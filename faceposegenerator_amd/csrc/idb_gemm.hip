@@ -1867,6 +1867,10 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
             IDB_REQUIRE(d->out_h == (lh + d->stride - 1) / d->stride && d->out_w == (lw + d->stride - 1) / d->stride,
                         "idb_gemm: src[%d] %dx%d (up=%d, stride=%d) does not produce %dx%d", s, S.in_h, S.in_w,
                         S.upsample, d->stride, d->out_h, d->out_w);
+        } else if (d->stride == 2 && d->pad_mode == 0 && S.upsample == 0 && (lh != d->out_h || lw != d->out_w)) {
+            // 1x1 source at stride 2 (a strided shortcut beside a stride-2 3x3 source): output pixel (oy, ox) reads (2 oy, 2 ox)
+            IDB_REQUIRE(d->out_h == (lh + 1) / 2 && d->out_w == (lw + 1) / 2,
+                        "idb_gemm: stride-2 1x1 src[%d] %dx%d does not produce %dx%d", s, S.in_h, S.in_w, d->out_h, d->out_w);
         } else {
             IDB_REQUIRE(d->stride == 1 && lh == d->out_h && lw == d->out_w,
                         "idb_gemm: 1x1 src[%d] must match the output grid", s);
@@ -1883,7 +1887,21 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
         IDB_REQUIRE(d->out_ld % 4 == 0, "idb_gemm: GEGLU out_ld must be a multiple of 4");
     }
     if (d->n % 4 == 0) IDB_REQUIRE(d->out_ld % 4 == 0, "idb_gemm: out_ld must be a multiple of 4 when n is");
-    IDB_REQUIRE(d->act == 0 || (d->act == 1 && !d->geglu && !d->residual), "idb_gemm: act must be 0, or 1 (GELU) without GEGLU/residual");
+    IDB_REQUIRE(d->act == 0 || d->act == 2 || (d->act == 1 && !d->geglu && !d->residual), "idb_gemm: act must be 0, or 1 (GELU) without GEGLU/residual");
+    if (d->act == 2)
+        IDB_REQUIRE(d->act_slope && idb_aligned16(d->act_slope) && !d->geglu && !d->residual && !d->ln_stats && !d->gn_in_partials &&
+                        !d->gn_partials && d->n % 4 == 0,
+                    "idb_gemm: act 2 (PReLU) needs a 16-byte aligned act_slope, n %% 4 == 0, and no residual / GEGLU / LayerNorm / GroupNorm fold / gn_partials");
+    if (d->out2 || d->out2_scale || d->out2_shift)
+        IDB_REQUIRE(d->out2 && d->out2_scale && d->out2_shift && idb_aligned16(d->out2) && idb_aligned16(d->out2_scale) &&
+                        idb_aligned16(d->out2_shift) && d->out_dtype == d->dtype && !d->geglu && !d->gn_partials && !d->row_stats_out &&
+                        !d->ln_stats && !d->gn_in_partials && d->n % 4 == 0,
+                    "idb_gemm: out2 needs 16-byte aligned out2, out2_scale and out2_shift, operand-dtype output, n %% 4 == 0, and no GEGLU / "
+                    "gn_partials / row_stats_out / LayerNorm / GroupNorm fold");
+    if (d->act == 2 || d->out2)
+        IDB_REQUIRE(d->out_dtype == d->dtype && (!d->bias || idb_aligned16(d->bias)) && (!d->residual || ((uintptr_t)d->residual & 7) == 0) &&
+                        (!d->sample_bias || (idb_aligned16(d->sample_bias) && d->sample_bias_ld % 4 == 0)),
+                    "idb_gemm: act 2 / out2 need operand-dtype output, a 16-byte aligned bias / sample_bias (ld %% 4 == 0), an 8-byte aligned residual");
     if (d->sample_bias) IDB_REQUIRE(d->sample_bias_ld == 0 || d->sample_bias_ld >= d->n, "idb_gemm: sample_bias_ld must be 0 (broadcast) or >= n");
 
     IDB_REQUIRE(((long long)d->n + 15) / 16 * 16 * K * 2 < (1LL << 31), "idb_gemm: weight matrix is >= 2 GiB");
@@ -1891,10 +1909,14 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
     pl->M = (int)M;
     pl->K = K;
     pl->ktiles = (int)(K / 64);
+    // PReLU / second output: applied by the reduce launch of a split-K plan (idb_splitk_reduce_ex_kernel), so the GEMM kernels keep
+    // their epilogues (and register budgets) as they are
+    const bool ex = d->act == 2 || d->out2;
+    IDB_REQUIRE(!ex || pl->ktiles >= 2, "idb_gemm: act 2 / out2 need K >= 128 (they run on a split-K plan)");
     const Variant* v = find_variant(d->tile);                // forced tile id; 0: chosen by the rules below
     IDB_REQUIRE(d->tile == 0 || v, "idb_gemm: tile id out of range");
     const bool plain = d->nsrc == 1 && d->src[0].taps == 1 && d->src[0].in_h == 1 && d->src[0].in_w == 1;
-    const bool pl_ok = plain && d->split_k <= 1 && d->out_dtype == d->dtype && (d->geglu ? d->n / 2 : d->n) % 4 == 0 &&
+    const bool pl_ok = plain && d->split_k <= 1 && d->out_dtype == d->dtype && (d->geglu ? d->n / 2 : d->n) % 4 == 0 && d->act != 2 && !d->out2 &&
                        d->out_ld % 4 == 0 && M * d->out_ld * 2 < (1LL << 31);
     IDB_REQUIRE(!v || v->fam != kPersistent || pl_ok, "idb_gemm: the persistent variant needs one plain [M][K] source, operand-dtype output < 2 GiB, no split-K");
     const PlanEnv& env = plan_env();
@@ -2002,7 +2024,7 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
             const long long blocks256 = ((M + 255) / 256) * ((d->n + 32 * kShapes[tile].nf - 1) / (32 * kShapes[tile].nf));
             if (env.big_tiles > 0 && blocks256 >= env.big_tiles) fam = kLw256;
             // 3x3 stride-1 convs on that plan: the patch-resident form (idb_conv_patch_kernel).  IDB_CONV_PATCH=0: tap-major 256-row tiles
-            if (fam == kLw256 && env.patch && d->split_k <= 1 && conv_patch_ok(d, M, 256)) fam = kPatch256;
+            if (fam == kLw256 && env.patch && d->split_k <= 1 && !ex && conv_patch_ok(d, M, 256)) fam = kPatch256;
         }
         // the same for the one-workgroup-per-CU plans (64- / 128-row tiles, split-K by whole chunks): IDB_CONV_PATCH_SMALL=1
         if (fam >= kLw3x4 && fam <= kLw4x4 && !d->geglu && (env.patch_small || d->gn_in_partials) &&
@@ -2012,6 +2034,7 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
         IDB_REQUIRE(v, "idb_gemm: the A/B switches chose tile %d, which is not built", tile + 10 * fam);
     }
     if (d->geglu) IDB_REQUIRE(v->nf % 2 == 0, "idb_gemm: GEGLU needs an even-NF tile");
+    IDB_REQUIRE(!ex || (v->fam != kPersistent && v->fam != kPatch256), "idb_gemm: act 2 / out2 need a split-K capable tile (not the persistent or 256-row patch-resident variant)");
     if ((v->fam == kPatch256 && !(d->split_k <= 1 && conv_patch_ok(d, M, 256))) || (v->fam == kPatchSmall && !conv_patch_ok(d, M, v->bm))) {
         idb_set_error("idb_gemm: tile %d (patch-resident conv) needs a 3x3 stride-1 pad-1 first source, 1x1 / 3x3 sources on the output grid without "
                       "upsampling, out_w in {8,16,32,64}, whole tiles of 256 pixels, no folded LayerNorm / fused GroupNorm / GEGLU / split-K", d->tile);
@@ -2046,6 +2069,7 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
     if (v->fam == kPersistent || v->fam == kPatch256) sk = 1;
     IDB_REQUIRE(!(d->geglu && sk > 1), "idb_gemm: GEGLU does not support split-K");
     if (d->act) sk = 1;
+    if (ex && sk < 2) sk = 2;          // act 2 / out2: the reduce launch applies them
     if (sk > pl->ktiles) sk = pl->ktiles;
     if (sk < 1) sk = 1;
     if (d->split_k <= 0 && !(d->flags & 16) && v->xcd_round && env.xcd_slices) {
@@ -2074,6 +2098,58 @@ static bool gemm_uses_lds_epilogue(const idb_gemm_desc* d, const Plan& pl) {
     return pl.v->fam != kRegStaged && lds_epilogue_runs(d, *pl.v, pl.splitk == 1);
 }
 
+// Split-K tail of the PReLU / second-output plans (idb_gemm_desc.act = 2, out2; ArcFace IResNet blocks): one thread per output row and
+// 4 channels sums the slabs in ascending split order, then v = sum*scale + bias (+ per-sample bias); PReLU; + residual; ONE rounding;
+// out2 = fma(rounded, out2_scale, out2_shift) rounded once.  n % 4 == 0 and out_ld % 4 == 0 (checked on the host); the slab and vector
+// loads are issued together as in idb_splitk_reduce_kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void idb_splitk_reduce_ex_kernel(const float* __restrict__ partial, int splitk, int M, int N, int HW,
+                                                                   float scale, const float* bias, const float* sbias, int sbias_ld,
+                                                                   const T* res, T* out, int out_ld, const float* slope, T* out2,
+                                                                   const float* out2_scale, const float* out2_shift) {
+    using V4 = typename Op<T>::v4;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)M * (N / 4)) return;
+    const int m = (int)(idx / (N / 4)), n = (int)(idx - (long long)m * (N / 4)) * 4;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 bi = zero, sbv = zero, sl = zero;
+    V4 r4;
+    if (res) r4 = *(const V4*)(res + (long long)m * out_ld + n);
+    if (bias) bi = *(const f32x4*)(bias + n);
+    if (sbias) sbv = *(const f32x4*)(sbias + (long long)(m / HW) * sbias_ld + n);
+    if (slope) sl = *(const f32x4*)(slope + n);
+    const float* src = partial + (long long)m * N + n;
+    const long long slab = (long long)M * N;
+    f32x4 v = zero;
+    for (int z0 = 0; z0 < splitk; z0 += 8) {
+        f32x4 t[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t[u] = *(const f32x4*)(src + (long long)min(z0 + u, splitk - 1) * slab);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const bool in = z0 + u < splitk;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] += in ? t[u][e] : 0.f;
+        }
+    }
+    V4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float x = v[e] * scale + bi[e] + sbv[e];
+        if (slope && x < 0.f) x *= sl[e];
+        if (res) x += to_f32<T>(r4[e]);
+        o[e] = from_f32<T>(x);
+    }
+    *(V4*)(out + (long long)m * out_ld + n) = o;
+    if (out2) {
+        const f32x4 a = *(const f32x4*)(out2_scale + n), b = *(const f32x4*)(out2_shift + n);
+        V4 o2;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o2[e] = affine_round<T>(to_f32<T>(o[e]), a[e], b[e]);
+        *(V4*)(out2 + (long long)m * out_ld + n) = o2;
+    }
+}
+
 template <typename T>
 int launch_all(const idb_gemm_desc* d, const GemmParams& p, const Plan& pl, hipStream_t st) {
     constexpr int dt = std::is_same<T, __bf16>::value ? 0 : 1;
@@ -2084,6 +2160,14 @@ int launch_all(const idb_gemm_desc* d, const GemmParams& p, const Plan& pl, hipS
     }
     const int rc = launch(*pl.v, p, pl, st);
     if (rc != IDB_OK || (d->flags & 1)) return rc;
+    if (d->act == 2 || d->out2) {
+        const long long total = (long long)pl.M * (d->n / 4);
+        hipLaunchKernelGGL((idb_splitk_reduce_ex_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.partial, pl.splitk, pl.M,
+                           d->n, p.HW, p.scale, p.bias, p.sbias, p.sbias_ld, (const T*)p.res, (T*)p.out, p.out_ld,
+                           d->act == 2 ? d->act_slope : nullptr, (T*)d->out2, d->out2_scale, d->out2_shift);
+        IDB_CHECK_LAUNCH("idb_splitk_reduce_ex");
+        return IDB_OK;
+    }
     return idb_finish_splitk<T>(p, pl.M, d->n, d->batch, pl.splitk, d->gn_partials, d->gn_groups, d->dtype, st);
 }
 
@@ -2232,7 +2316,7 @@ extern "C" int idb_gemm(const idb_gemm_desc* d, void* workspace, size_t workspac
         // The path is kept, tested bit-identical to the two-launch form, for shapes where a launch boundary is dearer.
         const int env_fused = plan_env().fused_reduce;
         const bool want_fused = (d->flags & 16) || (env_fused > 0 && pl.splitk <= env_fused);
-        const bool fused_reduce = pl.splitk > 1 && d->counters && want_fused && !(d->flags & 8) && !(d->flags & 1) &&
+        const bool fused_reduce = pl.splitk > 1 && d->counters && want_fused && !(d->flags & 8) && !(d->flags & 1) && d->act != 2 && !d->out2 &&
                                   (long long)pl.tiles_m * pl.tiles_n <= d->counters_len;
         p.counters = fused_reduce ? d->counters : nullptr;
         p.lds_epi = lds_epilogue_runs(d, *pl.v, pl.splitk == 1 || fused_reduce) ? 1 : 0;

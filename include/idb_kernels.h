@@ -54,7 +54,8 @@ int idb_device_check(int device);
  * to IDB_MAX_SRC sources, each contributing taps*channels columns ordered [tap][channel]:
  *   taps = 9 : 3x3 window with zero padding 1 read from an NHWC tensor [batch][in_h][in_w][channels]
  *              (upsample = 1: the tensor is logically nearest-2x upsampled first);
- *   taps = 1 : the pixel itself (1x1 conv, or a plain [M][K] matrix with in_h = in_w = 1).
+ *   taps = 1 : the pixel itself (1x1 conv, or a plain [M][K] matrix with in_h = in_w = 1); in a stride-2 GEMM (pad_mode 0) a 1x1
+ *              source may instead sit on the input grid (out = ceil(in / 2)) and read pixel (2 oy, 2 ox): the strided shortcut.
  * Several sources give skip-concatenation and the fused 1x1 shortcut without a concat pass.
  * channels must be a multiple of 64 for every source.
  * ------------------------------------------------------------------------------------------ */
@@ -143,6 +144,16 @@ typedef struct {
     float gn_in_eps;
     const float* gn_in_gamma;
     const float* gn_in_beta;
+    /* PReLU epilogue (act = 2; ArcFace IResNet): v = acc*out_scale + bias (+ per-sample bias), then v >= 0 ? v : v*act_slope[n], before
+     * the one rounding.  fp32 [n], 16-byte aligned; not with residual / GEGLU / a folded LayerNorm or GroupNorm.  Every plan applies it,
+     * split-K ones in their reduce launch. */
+    const float* act_slope;
+    /* Second, affine output: out2[m][n] = fma(float(out[m][n]), out2_scale[n], out2_shift[n]) computed on the ROUNDED primary output and
+     * rounded once to the operand dtype (the eval-mode BatchNorm that feeds the next zero-padded conv; ArcFace IBasicBlock.bn1), row stride
+     * out_ld, 16-byte aligned.  All three or none; operand-dtype output, n % 4 == 0, no GEGLU / gn_partials / row_stats_out.  NULL: off. */
+    void* out2;
+    const float* out2_scale;
+    const float* out2_shift;
 } idb_gemm_desc;
 
 size_t idb_gemm_workspace_bytes(const idb_gemm_desc* d);
@@ -354,6 +365,24 @@ int idb_groupnorm_fp8(const void* x0, int32_t c0, const void* x1, int32_t c1, in
                       void* workspace, size_t workspace_bytes, const float* partials_in, int32_t partials_chunks, void* stream);
 int idb_pack_weight_fp8(const float* src, void* dst, float* scales, int32_t cout, int32_t cin, int32_t ktaps, void* stream);
 int idb_gemm_fp8(const idb_gemm_fp8_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * ArcFace IResNet (insightface arcface_torch iresnet.py; ID-Booth's identity network) — the layers that are not idb_gemm calls.
+ *   idb_arcface_stem: conv1 3->64 (3x3, stride 1, pad 1) with bn1 folded into `weight` (fp32 [64][3][3][3] as [cout][ky][kx][cin]) and
+ *       `bias` (fp32 [64]), then PReLU (`slope` [64]).  x: uint8 NHWC crops [batch][h][w][3] when x_u8 (preprocessing
+ *       (x / 255 - 0.5) / 0.5 fused), else normalised fp32 NCHW [batch][3][h][w]; the input is rounded to the operand dtype first.
+ *       out: NHWC [batch][h][w][64] operand dtype; out2 (optional, as idb_gemm_desc.out2): fma(out, out2_scale, out2_shift) rounded.
+ *       w <= 256.
+ *   idb_arcface_head: y[m][n] = sum_k float(x[m][k]) * w[n][k] + bias[n] in fp32 (head bn2 + fc + features folded into w / bias),
+ *       x operand dtype [m][k], w fp32 [n][k]; n % 64 == 0, k % 32 == 0; K-sliced with a deterministic reduce through `workspace`
+ *       (idb_arcface_head_workspace_bytes).
+ * ------------------------------------------------------------------------------------------ */
+int idb_arcface_stem(const void* x, int32_t x_u8, int32_t batch, int32_t h, int32_t w, const float* weight, const float* bias,
+                     const float* slope, const float* out2_scale, const float* out2_shift, void* out, void* out2, int32_t dtype,
+                     void* stream);
+size_t idb_arcface_head_workspace_bytes(int32_t m, int32_t n, int32_t k);
+int idb_arcface_head(const void* x, const float* w, const float* bias, float* y, int32_t m, int32_t n, int32_t k, int32_t dtype,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 int idb_vae_sample(const float* moments, const float* noise, float scale, float* latents, float* mean_out,
                    float* logvar_out, int32_t batch, int32_t channels, int32_t hw, void* stream);
