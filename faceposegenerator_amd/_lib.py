@@ -29,6 +29,7 @@ EXPORTS = [
     "idb_crop_resize_area_u8", "idb_conv2d_f32", "idb_maxpool2d_f32", "idb_softmax_pairs_f32", "idb_nms_mask",
     "idb_quantize_fp8", "idb_pack_weight_fp8", "idb_gemm_fp8", "idb_groupnorm_fp8",
     "idb_arcface_stem", "idb_arcface_head_workspace_bytes", "idb_arcface_head",
+    "idb_resize_aa_u8", "idb_pose_stem", "idb_pose_head",
 ]
 
 
@@ -131,6 +132,9 @@ def load() -> C.CDLL:
         "idb_arcface_stem": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
         "idb_arcface_head_workspace_bytes": (sz, [i32, i32, i32]),
         "idb_arcface_head": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+        "idb_resize_aa_u8": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
+        "idb_pose_stem": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
+        "idb_pose_head": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

@@ -29,200 +29,18 @@
 
 // __launch_bounds__(256, 2): at most 256 VGPRs so that TWO workgroups share a CU — the second workgroup's MFMAs are what
 // hides this one's LDS-DMA issue, waits and epilogue (one workgroup per CU measured 0.70 vs 1.12 PFLOP/s on the conv shape).
+// idb_gemm_kernel and its ReLU twin (idb_gemm_desc.act = 3) share one body (idb_gemm_ring_body.inc); the epilogue activation is a
+// compile-time parameter, so the kernels without it keep their code and register budgets.
 template <typename T, int MF, int NF, int NS, int WM = 2>   // WM wave rows x 2 wave columns; tile = (16*MF*WM) x (32*NF)
 __global__ __launch_bounds__(128 * WM, 2) void idb_gemm_kernel(const GemmParams p) {
-#if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (buffer-resource types are device-only)
-    using V8 = typename Op<T>::v8;
-    constexpr int BM = 16 * MF * WM, BN = 32 * NF;
-    constexpr int THREADS = 128 * WM, RS = 16 * WM;          // staging: RS tile rows per wave-instruction sweep of the workgroup
-    constexpr int NJ = (BN + RS - 1) / RS;                   // weight-row sweeps; the last may be partial (160 rows / 64): its surplus
-    constexpr int STAGE = (BM + NJ * RS) * 128;              // rows are LDS padding filled with zeros (out-of-range voffset), so every
-                                                             // wave issues the same number of loads and the counted vmcnt stays exact
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+    [[maybe_unused]] constexpr bool RELU = false;
+#include "idb_gemm_ring_body.inc"
+}
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int fr = lane & 15, fg = lane >> 4;
-
-    // XCD-aware bijective remaps (workgroups are dealt round-robin over the 8 XCDs in linear-id order, so ids b and b+8 share
-    // an XCD and its L2; the 8 L2s are not coherent and do not share lines).
-    //  mode 0: each XCD gets a contiguous run of tiles, so neighbours re-use the same activation rows from that L2; the K
-    //          split, if any, is the grid's z.
-    //  mode 1 (split-K, S % 8 == 0) / mode 2 (S == 4): each XCD owns ONE K-slice (mode 2: half the tiles of one) of EVERY
-    //          tile, so every weight and activation byte crosses the fabric once instead of once per XCD — on the batch-1
-    //          weight-streaming layers (M = 512: 4 row tiles on 4 XCD pairs) mode 0 fetched the weights 4-8 times
-    //          (rocprofv3 FETCH_SIZE: 99-113 MB per launch against 28-40 MB of operands).
-    int wg, kz;
-    if (p.xcd_mode == 0) {
-        const int nwg = gridDim.x, orig = blockIdx.x;
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-        wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-        kz = blockIdx.z;
-    } else {
-        const int X = gridDim.x;
-        const int lin = blockIdx.x + X * blockIdx.z;
-        const int xcd = lin & 7, j = lin >> 3;
-        if (p.xcd_mode == 1) {
-            kz = xcd + 8 * (j / X);
-            wg = j % X;
-        } else {
-            kz = xcd >> 1;
-            wg = (xcd & 1) * (X >> 1) + j;
-        }
-    }
-    const int tm = wg / p.tiles_n, tn = wg - tm * p.tiles_n;
-    const int m0 = tm * BM, n0 = tn * BN;
-
-    const int kt0 = (int)(((long long)kz * p.ktiles) / p.splitk);          // balanced partition: slice sizes differ by at most one
-    const int kt1 = (int)(((long long)(kz + 1) * p.ktiles) / p.splitk);
-    const int nk = kt1 - kt0;
-
-    // ---- per-thread staging coordinates: thread loads chunk position (tid&7) of rows (tid>>3)+32i;
-    // the 16-byte chunk it fetches is (tid&7) ^ (row&7): the swizzle lives on the source address.
-    const int lrow = tid >> 3;
-    const unsigned cg16 = ((tid & 7) ^ (lrow & 7)) * 16;
-    int a_b[MF], a_oy[MF], a_ox[MF];
-    bool a_ok[MF];
-#pragma unroll
-    for (int i = 0; i < MF; ++i) {
-        const int m = m0 + i * RS + lrow;
-        a_ok[i] = m < p.M;
-        const int mm = a_ok[i] ? m : 0;
-        if (p.HW == 1) {                     // plain [M][K] matrix: no pixel decode (two integer divisions per row)
-            a_b[i] = mm;
-            a_oy[i] = a_ox[i] = 0;
-        } else {
-            a_b[i] = mm / p.HW;
-            const int rem = mm - a_b[i] * p.HW;
-            a_oy[i] = rem / p.OW;
-            a_ox[i] = rem - a_oy[i] * p.OW;
-        }
-    }
-    // weights: one descriptor, per-row voffset fixed for the whole K loop, K position in the SGPR soffset
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w + idb_weight_group(p, m0) * p.w_group_stride), 0, p.w_bytes, IDB_RSRC_FLAGS);
-    unsigned w_voff[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int n = n0 + j * RS + lrow;
-        w_voff[j] = (n < p.N && j * RS + lrow < BN) ? (unsigned)(n >> 4) * p.w_blk_bytes + (unsigned)(n & 15) * p.w_row_bytes + cg16 : IDB_OOB;
-    }
-    unsigned w_soff = (unsigned)kt0 * p.w_kstep;
-
-    // ---- K-step state: source s, tap (0..8; a 1x1 source sits on the centre tap 4), channel offset c0.
-    // Per-row voffsets (pixel address, zero padding -> out-of-range) are recomputed only when the tap or the
-    // source changes (every C/64 K-steps); inside a tap the channel offset rides in the SGPR soffset, so a
-    // K-step costs no address VALU at all.
-    int s = 0, tap = 0, c0 = 0, cur_c = 64, tap_end = 9;
-    {
-        int rem = kt0;
-        while (s < IDB_MAX_SRC - 1) {
-            const int steps = p.src[s].taps * (p.src[s].C >> 6);
-            if (rem < steps) break;
-            rem -= steps;
-            ++s;
-        }
-        const int cs = p.src[s].C >> 6;
-        if (p.src[s].taps == 9) {
-            tap = rem / cs;
-            c0 = (rem - tap * cs) << 6;
-        } else {
-            tap = 4;
-            c0 = rem << 6;
-        }
-    }
-    __amdgpu_buffer_rsrc_t rs_a = rs_w;
-    unsigned a_voff[MF];
-    bool need_retap = true;
-    auto retap = [&]() {
-        const GemmSrcK S = p.src[s];
-        rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)S.ptr, 0, S.bytes, IDB_RSRC_FLAGS);
-        cur_c = S.C;
-        tap_end = S.taps == 9 ? 9 : 5;
-        const int t3 = tap / 3;
-        const int dy = t3 - p.pad, dx = tap - t3 * 3 - p.pad;
-        const int LH = S.H << S.up, LW = S.W << S.up;
-#pragma unroll
-        for (int i = 0; i < MF; ++i) {
-            const int iy = a_oy[i] * p.stride + dy, ix = a_ox[i] * p.stride + dx;
-            const bool ok = a_ok[i] && (unsigned)iy < (unsigned)LH && (unsigned)ix < (unsigned)LW;
-            const int pix = (a_b[i] * S.H + (iy >> S.up)) * S.W + (ix >> S.up);
-            a_voff[i] = ok ? (unsigned)pix * (unsigned)(S.C * 2) + cg16 : IDB_OOB;
-        }
-    };
-    auto stage = [&](int buf) {
-        char* sA = smem + buf * STAGE;
-        char* sB = sA + BM * 128;
-        if (need_retap) {
-            retap();
-            need_retap = false;
-        }
-        const unsigned a_soff = (unsigned)c0 * 2u;
-#pragma unroll
-        for (int i = 0; i < MF; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, LDS_PTR(sA + (i * THREADS + wave * 64) * 16), 16, a_voff[i], a_soff, 0, 0);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, LDS_PTR(sB + (j * THREADS + wave * 64) * 16), 16, w_voff[j], w_soff, 0, 0);
-        w_soff += p.w_kstep;
-        c0 += 64;
-        if (c0 == cur_c) {
-            c0 = 0;
-            need_retap = true;
-            if (++tap == tap_end) {
-                if (s < IDB_MAX_SRC - 1) ++s;
-                tap = p.src[s].taps == 9 ? 0 : 4;
-            }
-        }
-    };
-
-    f32x4 acc[MF][NF];
-#pragma unroll
-    for (int i = 0; i < MF; ++i)
-#pragma unroll
-        for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    // ---- NS-deep LDS ring, one barrier per K-step.  At the top of iteration `it` tiles it .. it+NS-2 are in
-    // flight; the counted vmcnt retires tile `it` (this wave's share), the barrier makes every wave's share
-    // visible AND proves that all waves are done reading tile it-1, whose buffer the next DMA overwrites.
-    constexpr int LOADS = MF + NJ;
-#pragma unroll
-    for (int st = 0; st < NS - 1; ++st)
-        if (st < nk) stage(st);
-    // folded LayerNorm: this thread's share of its tile row's statistics, the loads in flight with the first operand tiles
-    float2 ln_part = make_float2(0.f, 0.f);
-    if (p.ln_stats) ln_part = idb_ln_row_partials<BM, THREADS>(p, m0, tid);
-    int cur = 0;
-    for (int it = 0; it < nk; ++it) {
-        if (NS > 2 && it + NS - 2 < nk)
-            asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((NS - 2) * LOADS) : "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        if (it + NS - 1 < nk && IDB_DBG(p.dbg_loop) != 2) stage(cur == 0 ? NS - 1 : cur - 1);
-        if (IDB_DBG(p.dbg_loop) == 1) {
-            cur = cur + 1 == NS ? 0 : cur + 1;
-            continue;
-        }
-        const char* sA = smem + cur * STAGE + (wm * 16 * MF + fr) * 128;
-        const char* sB = smem + cur * STAGE + BM * 128 + (wn * 16 * NF + fr) * 128;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int pos = ((ks * 4 + fg) ^ (fr & 7)) * 16;
-            V8 af[MF], wf[NF];
-#pragma unroll
-            for (int i = 0; i < MF; ++i) af[i] = *(const V8*)(sA + i * 16 * 128 + pos);
-#pragma unroll
-            for (int j = 0; j < NF; ++j) wf[j] = *(const V8*)(sB + j * 16 * 128 + pos);
-#pragma unroll
-            for (int i = 0; i < MF; ++i)
-#pragma unroll
-                for (int j = 0; j < NF; ++j) acc[i][j] = Op<T>::mfma16(wf[j], af[i], acc[i][j]);
-        }
-        cur = cur + 1 == NS ? 0 : cur + 1;
-    }
-
-    idb_gemm_epilogue<T, MF, NF, WM>(p, smem, acc, m0, n0, tid, wm, wn, fr, fg, kz, p.ln_stats != nullptr, ln_part);
-#endif
+template <typename T, int MF, int NF, int NS, int WM = 2>
+__global__ __launch_bounds__(128 * WM, 2) void idb_gemm_kernel_relu(const GemmParams p) {
+    [[maybe_unused]] constexpr bool RELU = true;
+#include "idb_gemm_ring_body.inc"
 }
 
 
@@ -239,8 +57,8 @@ __global__ __launch_bounds__(128 * WM, 2) void idb_gemm_kernel(const GemmParams 
 //   ring: NS stages; at the top of K-step `it` the loaders wait until stage `it` has landed (counted vmcnt: stages it+1 ..
 //   it+NS-2 stay in flight), the barrier publishes it and proves stage it-1 is read, then they issue stage it+NS-1 into that buffer.
 // ------------------------------------------------------------------------------------------------------------
-template <typename T, int MF, int NF, int NS, int WM, int LW>
-__global__ __launch_bounds__(128 * WM + 64 * LW) void idb_gemm_kernel_lw(const GemmParams p) {
+template <typename T, int MF, int NF, int NS, int WM, int LW, bool RELU>
+__device__ __forceinline__ void idb_gemm_kernel_lw_body(const GemmParams& p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using V8 = typename Op<T>::v8;
     constexpr int BM = 16 * MF * WM, BN = 32 * NF;
@@ -481,8 +299,18 @@ __global__ __launch_bounds__(128 * WM + 64 * LW) void idb_gemm_kernel_lw(const G
             cur = cur + 1 == NS ? 0 : cur + 1;
         }
     }
-    idb_gemm_epilogue<T, MF, NF, WM>(p, smem, acc, m0, n0, tid, wm, wn, fr, fg, kz, p.ln_stats != nullptr, ln_part);
+    idb_gemm_epilogue<T, MF, NF, WM, RELU>(p, smem, acc, m0, n0, tid, wm, wn, fr, fg, kz, p.ln_stats != nullptr, ln_part);
 #endif
+}
+
+template <typename T, int MF, int NF, int NS, int WM, int LW>
+__global__ __launch_bounds__(128 * WM + 64 * LW) void idb_gemm_kernel_lw(const GemmParams p) {
+    idb_gemm_kernel_lw_body<T, MF, NF, NS, WM, LW, false>(p);
+}
+
+template <typename T, int MF, int NF, int NS, int WM, int LW>
+__global__ __launch_bounds__(128 * WM + 64 * LW) void idb_gemm_kernel_lw_relu(const GemmParams p) {
+    idb_gemm_kernel_lw_body<T, MF, NF, NS, WM, LW, true>(p);
 }
 
 
@@ -1688,6 +1516,7 @@ struct Variant {
     bool xcd_round;                     // the planner rounds a heuristic split-K to one K-slice per XCD (S % 8 == 0 or S == 4)
     bool xcd_slices;                    // the kernel runs the K-slice-per-XCD remap (GemmParams.xcd_mode 1 / 2) when the split allows
     LaunchFn launch[2], launch_gn[2];   // [bf16, f16]; launch_gn: the fused-GroupNorm twin (nullptr: none)
+    LaunchFn launch_relu[2];            // the ReLU-epilogue twin (idb_gemm_desc.act = 3): ring and loader-wave families; nullptr: none
 };
 
 struct Plan {
@@ -1706,7 +1535,7 @@ size_t gn_fused_lds(const Variant& v, long long hw, long long cn, int groups) {
     return (size_t)v.gn_lds + (size_t)(nsamp * cn * 8) + (size_t)(nsamp * groups * 8);
 }
 
-template <typename T, Family F, int MF, int NF, int NS, int WM, int LW, bool GN>
+template <typename T, Family F, int MF, int NF, int NS, int WM, int LW, bool GN, bool RELU = false>
 int launch_variant(const Variant& v, const GemmParams& p, const Plan& pl, hipStream_t st) {
     const int tiles = pl.tiles_m * pl.tiles_n;
     const dim3 grid(tiles, 1, pl.splitk);
@@ -1723,12 +1552,16 @@ int launch_variant(const Variant& v, const GemmParams& p, const Plan& pl, hipStr
             return IDB_EUNSUPPORTED;
         }
         return idb_launch<idb_gemm_kernel_gn<T, 2, NF, 4, 2, 8>>("idb_gemm", "idb_gemm(gn)", grid, dim3(128 * 2 + 256 + 64 * 8), lds, 160 * 1024, st, p);
+    } else if constexpr (F <= kRing4 && RELU) {
+        return idb_launch<idb_gemm_kernel_relu<T, MF, NF, NS, WM>>("idb_gemm", "idb_gemm(relu)", grid, dim3(v.threads), v.lds, v.lds, st, p);
     } else if constexpr (F <= kRing4) {
         return idb_launch<idb_gemm_kernel<T, MF, NF, NS, WM>>("idb_gemm", "idb_gemm", grid, dim3(v.threads), v.lds, v.lds, st, p);
     } else if constexpr (F == kRegStaged) {
         return idb_launch<idb_gemm_kernel_rs<T, MF, NF>>("idb_gemm", "idb_gemm(rs)", grid, dim3(v.threads), v.lds, v.lds, st, p);
     } else if constexpr (F == kPersistent) {
         return idb_launch<idb_gemm_kernel_pl<T, MF, NF>>("idb_gemm", "idb_gemm(pl)", dim3(tiles < 512 ? tiles : 512), dim3(v.threads), v.lds, v.lds, st, p);
+    } else if constexpr (F <= kLw256 && RELU) {
+        return idb_launch<idb_gemm_kernel_lw_relu<T, MF, NF, NS, WM, LW>>("idb_gemm", "idb_gemm(lw, relu)", grid, dim3(v.threads), v.lds, v.lds, st, p);
     } else if constexpr (F <= kLw256) {
         return idb_launch<idb_gemm_kernel_lw<T, MF, NF, NS, WM, LW>>("idb_gemm", "idb_gemm(lw)", grid, dim3(v.threads), v.lds, v.lds, st, p);
     } else {
@@ -1749,13 +1582,18 @@ constexpr Variant variant() {
     constexpr int GN_LDS = !gn ? 0 : F == kPatchSmall ? patch_lds(MF, NF, NS, true) : (BM + (BN + 31) / 32 * 32) * 128 * 4;
     static_assert(LDS <= 160 * 1024 && GN_LDS <= 160 * 1024, "LDS does not fit");
     constexpr bool ring_or_lw = F <= kRing3 || F >= kLw3x4;
-    LaunchFn gn_bf16 = nullptr, gn_f16 = nullptr;
+    LaunchFn gn_bf16 = nullptr, gn_f16 = nullptr, relu_bf16 = nullptr, relu_f16 = nullptr;
     if constexpr (gn) {
         gn_bf16 = launch_variant<__bf16, F, MF, NF, NS, WM, LW, true>;
         gn_f16 = launch_variant<_Float16, F, MF, NF, NS, WM, LW, true>;
     }
+    if constexpr (F <= kRing4 || (F >= kLw3x4 && F <= kLw256)) {
+        relu_bf16 = launch_variant<__bf16, F, MF, NF, NS, WM, LW, false, true>;
+        relu_f16 = launch_variant<_Float16, F, MF, NF, NS, WM, LW, false, true>;
+    }
     return {S + 10 * F, F, MF, NF, NS, WM, LW, BM, BN, 128 * WM + 64 * LW, 128 * WM, LDS, GN_LDS, ring_or_lw && WM == 4, ring_or_lw && S != 5,
-            {launch_variant<__bf16, F, MF, NF, NS, WM, LW, false>, launch_variant<_Float16, F, MF, NF, NS, WM, LW, false>}, {gn_bf16, gn_f16}};
+            {launch_variant<__bf16, F, MF, NF, NS, WM, LW, false>, launch_variant<_Float16, F, MF, NF, NS, WM, LW, false>}, {gn_bf16, gn_f16},
+            {relu_bf16, relu_f16}};
 }
 
 constexpr Variant kVariants[] = {
@@ -1887,7 +1725,9 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
         IDB_REQUIRE(d->out_ld % 4 == 0, "idb_gemm: GEGLU out_ld must be a multiple of 4");
     }
     if (d->n % 4 == 0) IDB_REQUIRE(d->out_ld % 4 == 0, "idb_gemm: out_ld must be a multiple of 4 when n is");
-    IDB_REQUIRE(d->act == 0 || d->act == 2 || (d->act == 1 && !d->geglu && !d->residual), "idb_gemm: act must be 0, or 1 (GELU) without GEGLU/residual");
+    IDB_REQUIRE(d->act == 0 || d->act == 2 || ((d->act == 1 || d->act == 3) && !d->geglu && !d->residual),
+                "idb_gemm: act must be 0, 2, or 1 (GELU) / 3 (ReLU) without GEGLU/residual");
+    if (d->act == 3) IDB_REQUIRE(!d->gn_partials && !d->gn_in_partials, "idb_gemm: act 3 (ReLU) is not combined with gn_partials / gn_in_partials");
     if (d->act == 2)
         IDB_REQUIRE(d->act_slope && idb_aligned16(d->act_slope) && !d->geglu && !d->residual && !d->ln_stats && !d->gn_in_partials &&
                         !d->gn_partials && d->n % 4 == 0,
@@ -1916,7 +1756,7 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
     const Variant* v = find_variant(d->tile);                // forced tile id; 0: chosen by the rules below
     IDB_REQUIRE(d->tile == 0 || v, "idb_gemm: tile id out of range");
     const bool plain = d->nsrc == 1 && d->src[0].taps == 1 && d->src[0].in_h == 1 && d->src[0].in_w == 1;
-    const bool pl_ok = plain && d->split_k <= 1 && d->out_dtype == d->dtype && (d->geglu ? d->n / 2 : d->n) % 4 == 0 && d->act != 2 && !d->out2 &&
+    const bool pl_ok = plain && d->split_k <= 1 && d->out_dtype == d->dtype && (d->geglu ? d->n / 2 : d->n) % 4 == 0 && d->act != 2 && d->act != 3 && !d->out2 &&
                        d->out_ld % 4 == 0 && M * d->out_ld * 2 < (1LL << 31);
     IDB_REQUIRE(!v || v->fam != kPersistent || pl_ok, "idb_gemm: the persistent variant needs one plain [M][K] source, operand-dtype output < 2 GiB, no split-K");
     const PlanEnv& env = plan_env();
@@ -2034,6 +1874,7 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
         IDB_REQUIRE(v, "idb_gemm: the A/B switches chose tile %d, which is not built", tile + 10 * fam);
     }
     if (d->geglu) IDB_REQUIRE(v->nf % 2 == 0, "idb_gemm: GEGLU needs an even-NF tile");
+    IDB_REQUIRE(d->act != 3 || v->launch_relu[0], "idb_gemm: act 3 (ReLU) runs on the LDS-ring and loader-wave tiles only (tile %d)", v->id);
     IDB_REQUIRE(!ex || (v->fam != kPersistent && v->fam != kPatch256), "idb_gemm: act 2 / out2 need a split-K capable tile (not the persistent or 256-row patch-resident variant)");
     if ((v->fam == kPatch256 && !(d->split_k <= 1 && conv_patch_ok(d, M, 256))) || (v->fam == kPatchSmall && !conv_patch_ok(d, M, v->bm))) {
         idb_set_error("idb_gemm: tile %d (patch-resident conv) needs a 3x3 stride-1 pad-1 first source, 1x1 / 3x3 sources on the output grid without "
@@ -2068,7 +1909,7 @@ int plan_gemm(const idb_gemm_desc* d, Plan* pl) {
     }
     if (v->fam == kPersistent || v->fam == kPatch256) sk = 1;
     IDB_REQUIRE(!(d->geglu && sk > 1), "idb_gemm: GEGLU does not support split-K");
-    if (d->act) sk = 1;
+    if (d->act == 1 || d->act == 2) sk = 1;   // act 3 (ReLU) keeps its split: the reduce launch applies it after the sum
     if (ex && sk < 2) sk = 2;          // act 2 / out2: the reduce launch applies them
     if (sk > pl->ktiles) sk = pl->ktiles;
     if (sk < 1) sk = 1;
@@ -2153,7 +1994,7 @@ __global__ __launch_bounds__(256) void idb_splitk_reduce_ex_kernel(const float* 
 template <typename T>
 int launch_all(const idb_gemm_desc* d, const GemmParams& p, const Plan& pl, hipStream_t st) {
     constexpr int dt = std::is_same<T, __bf16>::value ? 0 : 1;
-    const LaunchFn launch = p.gn_in_part ? pl.v->launch_gn[dt] : pl.v->launch[dt];
+    const LaunchFn launch = p.gn_in_part ? pl.v->launch_gn[dt] : d->act == 3 ? pl.v->launch_relu[dt] : pl.v->launch[dt];
     if (!launch) {
         idb_set_error("idb_gemm: fused GroupNorm is built for 64-row tiles only");
         return IDB_EUNSUPPORTED;
@@ -2168,7 +2009,7 @@ int launch_all(const idb_gemm_desc* d, const GemmParams& p, const Plan& pl, hipS
         IDB_CHECK_LAUNCH("idb_splitk_reduce_ex");
         return IDB_OK;
     }
-    return idb_finish_splitk<T>(p, pl.M, d->n, d->batch, pl.splitk, d->gn_partials, d->gn_groups, d->dtype, st);
+    return idb_finish_splitk<T>(p, pl.M, d->n, d->batch, pl.splitk, d->gn_partials, d->gn_groups, d->dtype, st, d->act == 3);
 }
 
 }  // namespace

@@ -149,7 +149,7 @@ __device__ __forceinline__ void idb_load_colvecs(const GemmParams& p, int m0, in
     }
 }
 
-template <typename T, int MF, int NF, bool GEGLU, int WM = 2>
+template <typename T, int MF, int NF, bool GEGLU, int WM = 2, bool RELU = false>
 __device__ __forceinline__ void idb_lds_epilogue(const GemmParams& p, char* smem, f32x4 (&acc)[MF][NF], const f32x4 (&ca)[NF],
                                                  const f32x4 (&cb)[NF], int m0, int n0, int tid, int wm, int wn, int fr, int fg, bool ln = false,
                                                  float2 ln_part = {0.f, 0.f}) {
@@ -230,6 +230,10 @@ __device__ __forceinline__ void idb_lds_epilogue(const GemmParams& p, char* smem
                 if (p.act == 1) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = gelu_erf_f(o[e]);
+                }
+                if constexpr (RELU) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f);
                 }
                 if (p.res) {
                     const V4 r4 = *(const V4*)(smem + row * OLD + col * 2);
@@ -318,7 +322,7 @@ __device__ __forceinline__ void idb_lds_epilogue(const GemmParams& p, char* smem
 
 // Everything after the K loop: LDS-staged coalesced epilogue for operand-dtype outputs, direct epilogue for fp32 outputs /
 // split-K slabs / odd widths.  PRE: ca / cb were loaded by the kernel before its K loop (idb_load_colvecs).
-template <typename T, int MF, int NF, int WM = 2, bool PRE = false>
+template <typename T, int MF, int NF, int WM = 2, bool PRE = false, bool RELU = false>
 __device__ __forceinline__ void idb_gemm_epilogue(const GemmParams& p, char* smem, f32x4 (&acc)[MF][NF], f32x4 (&ca)[NF], f32x4 (&cb)[NF], int m0,
                                                   int n0, int tid, int wm, int wn, int fr, int fg, int kz, bool ln = false,
                                                   float2 ln_part = {0.f, 0.f}) {
@@ -412,9 +416,9 @@ __device__ __forceinline__ void idb_gemm_epilogue(const GemmParams& p, char* sme
     if (p.lds_epi) {
         if constexpr (!PRE) idb_load_colvecs<NF, 16 * MF * WM>(p, m0, n0, wn, fg, ca, cb);
         if (p.geglu) {
-            if constexpr ((NF & 1) == 0) idb_lds_epilogue<T, MF, NF, true, WM>(p, smem, acc, ca, cb, m0, n0, tid, wm, wn, fr, fg, ln, ln_part);
+            if constexpr ((NF & 1) == 0) idb_lds_epilogue<T, MF, NF, true, WM, RELU>(p, smem, acc, ca, cb, m0, n0, tid, wm, wn, fr, fg, ln, ln_part);
         } else {
-            idb_lds_epilogue<T, MF, NF, false, WM>(p, smem, acc, ca, cb, m0, n0, tid, wm, wn, fr, fg, ln, ln_part);
+            idb_lds_epilogue<T, MF, NF, false, WM, RELU>(p, smem, acc, ca, cb, m0, n0, tid, wm, wn, fr, fg, ln, ln_part);
         }
         return;
     }
@@ -471,6 +475,10 @@ __device__ __forceinline__ void idb_gemm_epilogue(const GemmParams& p, char* sme
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = gelu_erf_f(o[e]);
                 }
+                if constexpr (RELU) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f);
+                }
                 if (p.res) {
                     const typename Op<T>::v4 r4 = *(const typename Op<T>::v4*)((const T*)p.res + (long long)m * p.out_ld + n);
 #pragma unroll
@@ -490,6 +498,7 @@ __device__ __forceinline__ void idb_gemm_epilogue(const GemmParams& p, char* sme
                     if (p.bias) v += p.bias[n + e];
                     if (sb) v += sb[n + e];
                     if (p.act == 1) v = gelu_erf_f(v);
+                    if constexpr (RELU) v = fmaxf(v, 0.f);
                     if (p.res) v += to_f32<T>(((const T*)p.res)[(long long)m * p.out_ld + n + e]);
                     if (p.out_f32) ((float*)p.out)[(long long)m * p.out_ld + n + e] = v;
                     else ((T*)p.out)[(long long)m * p.out_ld + n + e] = from_f32<T>(v);
@@ -502,11 +511,11 @@ __device__ __forceinline__ void idb_gemm_epilogue(const GemmParams& p, char* sme
 // the form every kernel uses: column vectors loaded at the head of the epilogue.  (PRE = loading them before the K loop of the
 // 64-row tiles, older than every LDS-DMA, was measured: batch 1 6.653 -> 6.630 images/s, batch 8 13.85 -> 13.68 — the 16-40 more
 // live VGPRs and the later first DMA cost more than the one L2 round trip saved.)
-template <typename T, int MF, int NF, int WM = 2>
+template <typename T, int MF, int NF, int WM = 2, bool RELU = false>
 __device__ __forceinline__ void idb_gemm_epilogue(const GemmParams& p, char* smem, f32x4 (&acc)[MF][NF], int m0, int n0, int tid, int wm, int wn,
                                                   int fr, int fg, int kz, bool ln = false, float2 ln_part = {0.f, 0.f}) {
     f32x4 ca[NF], cb[NF];
-    idb_gemm_epilogue<T, MF, NF, WM, false>(p, smem, acc, ca, cb, m0, n0, tid, wm, wn, fr, fg, kz, ln, ln_part);
+    idb_gemm_epilogue<T, MF, NF, WM, false, RELU>(p, smem, acc, ca, cb, m0, n0, tid, wm, wn, fr, fg, kz, ln, ln_part);
 }
 
 
@@ -516,11 +525,11 @@ __device__ __forceinline__ void idb_gemm_epilogue(const GemmParams& p, char* sme
 // a data-dependent loop or branch gets an s_waitcnt vmcnt(0) right behind it, and with 8-30 slabs the first version of this
 // kernel spent its time in that many dependent round trips.  Slabs are added in ascending split order (deterministic, and
 // bit-identical to the in-kernel reduce).  VEC = 1 is the scalar fallback for odd widths / unaligned residuals.
-template <typename T, int VEC>
-__global__ __launch_bounds__(256) void idb_splitk_reduce_kernel(const float* __restrict__ partial, int splitk,
-                                                                int M, int N, int HW, float scale,
-                                                                const float* bias, const float* sbias, int sbias_ld,
-                                                                const T* res, void* out, int out_ld, int out_f32) {
+// RELU: idb_gemm_desc.act = 3, max(v, 0) after the biases, before the one rounding (its own kernel, idb_splitk_reduce_relu_kernel).
+template <typename T, int VEC, bool RELU>
+__device__ __forceinline__ void idb_splitk_reduce_body(const float* __restrict__ partial, int splitk, int M, int N, int HW, float scale,
+                                                       const float* bias, const float* sbias, int sbias_ld, const T* res, void* out,
+                                                       int out_ld, int out_f32) {
     const long long total = (long long)M * N / VEC;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
@@ -553,6 +562,7 @@ __global__ __launch_bounds__(256) void idb_splitk_reduce_kernel(const float* __r
             v[e] *= scale;
             if (bias) v[e] += bi[e];
             if (sbias) v[e] += sbv[e];
+            if constexpr (RELU) v[e] = fmaxf(v[e], 0.f);
             if (res) v[e] += to_f32<T>(r4[e]);
         }
         if (out_f32) {
@@ -567,10 +577,27 @@ __global__ __launch_bounds__(256) void idb_splitk_reduce_kernel(const float* __r
         v *= scale;
         if (bias) v += bias[n];
         if (sbias) v += sbias[(long long)(m / HW) * sbias_ld + n];
+        if constexpr (RELU) v = fmaxf(v, 0.f);
         if (res) v += to_f32<T>(res[(long long)m * out_ld + n]);
         if (out_f32) ((float*)out)[(long long)m * out_ld + n] = v;
         else ((T*)out)[(long long)m * out_ld + n] = from_f32<T>(v);
     }
+}
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void idb_splitk_reduce_kernel(const float* __restrict__ partial, int splitk,
+                                                                int M, int N, int HW, float scale,
+                                                                const float* bias, const float* sbias, int sbias_ld,
+                                                                const T* res, void* out, int out_ld, int out_f32) {
+    idb_splitk_reduce_body<T, VEC, false>(partial, splitk, M, N, HW, scale, bias, sbias, sbias_ld, res, out, out_ld, out_f32);
+}
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void idb_splitk_reduce_relu_kernel(const float* __restrict__ partial, int splitk,
+                                                                     int M, int N, int HW, float scale,
+                                                                     const float* bias, const float* sbias, int sbias_ld,
+                                                                     const T* res, void* out, int out_ld, int out_f32) {
+    idb_splitk_reduce_body<T, VEC, true>(partial, splitk, M, N, HW, scale, bias, sbias, sbias_ld, res, out, out_ld, out_f32);
 }
 
 // Split-K tail that also emits the first GroupNorm pass of its output (idb_gemm_desc.gn_partials): one workgroup owns 64
@@ -694,7 +721,8 @@ inline bool idb_epilogue_emits_gn(int bm, int bn, int threads, long long M, int 
 // written in its window order, from the GEMM's own LDS-staged epilogue when there is no split (p.gn_part), by an extra statistics
 // launch otherwise).
 template <typename T>
-int idb_finish_splitk(const GemmParams& p, int M, int n, int batch, int splitk, float* gn_partials, int gn_groups, int dtype, hipStream_t st) {
+int idb_finish_splitk(const GemmParams& p, int M, int n, int batch, int splitk, float* gn_partials, int gn_groups, int dtype, hipStream_t st,
+                      bool relu = false) {
     if (gn_partials && !p.gn_part && (splitk == 1 || p.counters))
         return idb_launch_gn_stats64(p.out, n, batch, p.HW, gn_groups, gn_partials, dtype, st);   // no reduce launch to ride on
     if (splitk == 1 || p.counters) return IDB_OK;
@@ -708,6 +736,16 @@ int idb_finish_splitk(const GemmParams& p, int M, int n, int batch, int splitk, 
     const int vec = idb_reduce_vec_ok(p, n) ? 4 : 1;
     const long long total = (long long)M * n / vec;
     const int blocks = (int)((total + 255) / 256);
+    if (relu) {             // act = 3 (the host refuses it with gn_partials, so nothing follows)
+        if (vec == 4)
+            hipLaunchKernelGGL((idb_splitk_reduce_relu_kernel<T, 4>), dim3(blocks), dim3(256), 0, st, p.partial, splitk, M, n, p.HW, p.scale,
+                               p.bias, p.sbias, p.sbias_ld, (const T*)p.res, p.out, p.out_ld, p.out_f32);
+        else
+            hipLaunchKernelGGL((idb_splitk_reduce_relu_kernel<T, 1>), dim3(blocks), dim3(256), 0, st, p.partial, splitk, M, n, p.HW, p.scale,
+                               p.bias, p.sbias, p.sbias_ld, (const T*)p.res, p.out, p.out_ld, p.out_f32);
+        IDB_CHECK_LAUNCH("idb_splitk_reduce_relu");
+        return IDB_OK;
+    }
     if (vec == 4)
         hipLaunchKernelGGL((idb_splitk_reduce_kernel<T, 4>), dim3(blocks), dim3(256), 0, st, p.partial, splitk, M, n, p.HW, p.scale, p.bias,
                            p.sbias, p.sbias_ld, (const T*)p.res, p.out, p.out_ld, p.out_f32);

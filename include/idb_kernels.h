@@ -87,7 +87,9 @@ typedef struct {
     int32_t tile;             /* 0 = heuristic; else a tile config id as idb_gemm_plan reports it (tests and measurements) */
     float out_scale;          /* multiplies the accumulator before bias (0 => 1.0) */
     int32_t flags;            /* profiling/testing only — bit 0: skip the split-K reduce launch (`out` not written); bit 1: skip the epilogue stores; bit 2: force the direct (non-LDS-staged) epilogue; bit 3: force the two-launch split-K reduce; bit 4: in-kernel split-K reduce (default: separate reduce launch, which measured faster); bit 8: let the persistent variant fold a LayerNorm (ln_stats; default: IDB_EUNSUPPORTED there, the separate idb_layernorm measured no slower) */
-    int32_t act;              /* 0 none, 1 exact GELU applied to (acc*scale + bias) (CLIP MLP fc1); not with residual/GEGLU */
+    int32_t act;              /* 0 none, 1 exact GELU applied to (acc*scale + bias) (CLIP MLP fc1); not with residual/GEGLU;
+                               * 3 ReLU, the same place (RepVGG blocks): not with residual / GEGLU / gn_partials / gn_in_partials, on the
+                               * LDS-ring and loader-wave tiles; split-K plans apply it in their reduce; 2: see act_slope */
     uint32_t* counters;       /* optional: >= counters_len zeroed uint32 on the device, private to the stream; used only with
                                  flags bit 4: a split-K launch then reduces inside the GEMM (the last-arriving workgroup of a
                                  tile sums the slabs in fixed order and runs the epilogue; counters are left zero) */
@@ -383,6 +385,25 @@ int idb_arcface_stem(const void* x, int32_t x_u8, int32_t batch, int32_t h, int3
 size_t idb_arcface_head_workspace_bytes(int32_t m, int32_t n, int32_t k);
 int idb_arcface_head(const void* x, const float* w, const float* bias, float* y, int32_t m, int32_t n, int32_t k, int32_t dtype,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 6DRepNet head pose (sixdrepnet SixDRepNet_Detector: RepVGG-B1g2 deploy form + 6D rotation head; ID-Booth's pose evaluation) — the
+ * layers that are not idb_gemm calls (the 27 3x3 blocks are idb_gemm with act = 3).
+ *   idb_resize_aa_u8: uint8 HWC RGB [batch][s][s][3] -> constant-zero border of `pad` pixels -> Pillow's antialiased BILINEAR resize
+ *       (Image.resize((d, d), BILINEAR), 8-bit fixed point) -> [batch][d][d][3]; bit-exact with Pillow.  d <= 256, at most 16 taps
+ *       per axis ((s + 2 pad) / d <= 7).
+ *   idb_pose_stem: conv 3->64 (3x3, stride 2, pad 1) + bias + ReLU; weight fp32 [64][3][3][3] as [cout][ky][kx][cin].  x: uint8 NHWC
+ *       [batch][h][w][3] when x_u8 (ToTensor + ImageNet Normalize fused, fp32), else normalised fp32 NCHW [batch][3][h][w].
+ *       out: NHWC [batch][ceil(h/2)][ceil(w/2)][64] operand dtype.  w <= 512.
+ *   idb_pose_head: global average pool of x [batch][hw][c] (operand dtype, fixed summation order), linear c->6 (weight fp32 [6][c],
+ *       bias [6]), Gram-Schmidt to R (fp32 [batch][3][3], the columns x y z) and Euler angles (fp32 [batch][3]: pitch, yaw, roll in
+ *       degrees).  c % 8 == 0; deterministic.
+ * ------------------------------------------------------------------------------------------ */
+int idb_resize_aa_u8(const void* src, int32_t batch, int32_t s, int32_t pad, int32_t d, void* dst, void* stream);
+int idb_pose_stem(const void* x, int32_t x_u8, int32_t batch, int32_t h, int32_t w, const float* weight, const float* bias, void* out,
+                  int32_t dtype, void* stream);
+int idb_pose_head(const void* x, int32_t batch, int32_t hw, int32_t c, const float* weight, const float* bias, float* rot, float* angles,
+                  int32_t dtype, void* stream);
 
 int idb_vae_sample(const float* moments, const float* noise, float scale, float* latents, float* mean_out,
                    float* logvar_out, int32_t batch, int32_t channels, int32_t hw, void* stream);
