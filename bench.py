@@ -7,7 +7,14 @@ DDPM step) -> VAE decode -> uint8 images in HBM (+ one RCCL all-gather of the de
 Default workload = BASELINE configs[1] (batch 1 per GPU); `--batch 64` is configs[2], the throughput point.
 Weights are seeded synthetic tensors of the published SD-2.1-base shapes (no network for checkpoints).
 
+A plain run does only what the headline figure needs: set-up, the --warmup and --steps steps, --dump-outputs, and the result
+line (its `roofline` is the whole path's TFLOP/s of the timed steps).  `--full` adds what takes runs of its own: per-stage
+times (`path.stages`), for the default workload the batch-64 f16 and fp8 points and the driver points (`path.config2`,
+`path.config2_fp8`, `path.config2_mixed`, `path.driver_e2e`), the per-kernel roofline replay and the CPU baseline
+(`cpu_baseline`); each --no-* option leaves one of them out of a --full run.
+
   python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N ...          (no WORLD_SIZE in the environment: starts the N ranks itself through
@@ -73,12 +80,15 @@ def parse():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--tiny", action="store_true", help="reduced-width graph (plumbing check only; not a benchmark)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure the per-stage times, the batch-64 f16 / fp8 points and the driver points of the "
+                         "default workload, the per-kernel roofline and the CPU baseline (off: the headline figure alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-kernel-roofline", action="store_true", help="--full without the per-kernel roofline replay")
     ap.add_argument("--vae-chunk", type=int, default=4)
-    ap.add_argument("--no-config2", action="store_true", help="skip the short batch-64 (BASELINE configs[2]) timing of the default run")
-    ap.add_argument("--no-fp8-point", action="store_true", help="skip the batch-64 timing of the fp8 (e4m3 resnet convs) engine in the default run")
-    ap.add_argument("--no-driver-points", action="store_true", help="skip path.config2_mixed / path.driver_e2e (driver.generate with LoRA switches, text encoder, PNG sink)")
+    ap.add_argument("--no-config2", action="store_true", help="--full without the short batch-64 (BASELINE configs[2]) timing of the default run")
+    ap.add_argument("--no-fp8-point", action="store_true", help="--full without the batch-64 timing of the fp8 (e4m3 resnet convs) engine in the default run")
+    ap.add_argument("--no-driver-points", action="store_true", help="--full without path.config2_mixed / path.driver_e2e (driver.generate with LoRA switches, text encoder, PNG sink)")
     ap.add_argument("--cpu-baseline-threads", type=int, default=0, help="0 = all cores of the host (default); e.g. 8 for the build container's figure")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the images the last timed step returned to DIR/images.npy (float32, see dump_outputs)")
@@ -619,8 +629,9 @@ def main():
     flops_per_image = 2 * args.ddpm_steps * fl_unet + fl_vae
     arena_mib = None if fake else round(eng.arena.total_bytes / 2 ** 20, 1)
     default_workload = B == 1 and not args.tiny and args.ddpm_steps == 30 and args.size == 512 and not fake
+    extra_points = args.full and default_workload and world == 1          # the points below take runs of their own: --full only
     config2 = None
-    if default_workload and world == 1 and not args.no_config2:
+    if extra_points and not args.no_config2:
         # BASELINE configs[2] (batch 64 = the attention/conv throughput point), timed briefly in the same run so that the figure
         # is driver-observed: 1 warm-up call (eager pass + graph capture + replay) and 2 timed steps
         step64, _ = make_step(64)
@@ -632,7 +643,7 @@ def main():
                    "frac_of_mfma_peak": round(tf64 / PEAK_MFMA_TFLOPS, 4), "arena_mib": round(eng.arena.total_bytes / 2 ** 20, 1)}
 
     drv_points = None
-    if default_workload and world == 1 and not args.no_driver_points:
+    if extra_points and not args.no_driver_points:
         if config2 is not None:
             del step64
             step64 = None
@@ -641,7 +652,7 @@ def main():
         pipe.load_lora_weights(lora_raw)                   # back to this rank's identity for the stage timings below
 
     fp8_point = None
-    if default_workload and world == 1 and not args.no_config2 and not args.no_fp8_point and args.dtype == "f16":
+    if extra_points and not args.no_config2 and not args.no_fp8_point and args.dtype == "f16":
         # the same batch-64 point on the fp8 path (BASELINE configs[4]'s "fp8 MFMA weight path", here at 512x512 so that it sits beside
         # config2): a second engine with e4m3 resnet convs; its parity class is stated in DESIGN.md section 2.3 (opt-in, not the default)
         step64 = None
@@ -685,7 +696,7 @@ def main():
             res["path"] = {"algorithmic_tflop_per_image": round(flops_per_image / 1e12, 3), "tflops": round(path_tflops, 1),
                            "frac_of_mfma_peak": round(path_tflops / PEAK_MFMA_TFLOPS, 4), "gpu_ms_per_step": round(gpu_ms / args.steps, 3),
                            "load_pack_s": round(t_load, 1), "arena_mib": arena_mib}
-            if world == 1:
+            if args.full and world == 1:
                 res["path"]["stages"] = stage_times(pipe, eng, pe_d, ne_d, noise, args)
             if config2:
                 res["path"]["config2"] = config2
@@ -694,13 +705,13 @@ def main():
             if drv_points:
                 res["path"].update(drv_points)
                 res["path"]["stages"]["text_encoder_ms"] = round(2 * drv_points["driver_e2e"]["text_encoder_ms"] / drv_points["driver_e2e"]["text_encoder_prompts"], 3)   # prompt + negative prompt of one image
-            if not args.no_kernel_roofline:
+            if args.full and not args.no_kernel_roofline:
                 res["roofline"], dom = kernel_roofline(eng, B, lat_side, 77)
                 attach_profile_evidence(res["roofline"], dom, B, args)
             else:
                 res["roofline"] = {"bound": "mfma", "achieved": round(path_tflops, 1), "peak": PEAK_MFMA_TFLOPS, "unit": "TFLOP/s",
                                    "frac": round(path_tflops / PEAK_MFMA_TFLOPS, 4), "traffic": None}
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 res["cpu_baseline"] = cpu_baseline(pipe, ucfg, vcfg, lora_raw, args.ddpm_steps, args.size, args.cpu_baseline_threads)
         print(json.dumps(res), flush=True)
     if world > 1 or force_dist:

@@ -4,7 +4,7 @@ cd $R
 step() { log=$1; shift; "$@" > $R/gpurun_out/$log 2>&1; rc=$?; echo "[$log] rc=$rc"; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "timeout/kill: stopping"; tail -n 5 $R/gpurun_out/$log; exit $rc; fi; }
 step bd_contract.log timeout -k 10 400 python -m pytest tests/test_bench_contract_gpu.py tests/test_rccl_gpu.py -q -x
 tail -n 3 gpurun_out/bd_contract.log
-step bd_bench.log timeout -k 10 600 python bench.py
+step bd_bench.log timeout -k 10 600 python bench.py --full
 grep -h '^{' gpurun_out/bd_bench.log > gpurun_out/bd_bench.json
 python - <<'PY'
 import json

@@ -6,9 +6,9 @@ step fin_suite.log timeout -k 10 700 python -m pytest tests -q -m gpu
 tail -n 6 gpurun_out/fin_suite.log
 step fin_smoke.log timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()"
 tail -n 2 gpurun_out/fin_smoke.log
-step fin_bench_default.log timeout -k 10 600 python bench.py
+step fin_bench_default.log timeout -k 10 600 python bench.py --full
 grep -h '"value"' gpurun_out/fin_bench_default.log > gpurun_out/fin_bench_default.json
-step fin_bench_768fp8.log timeout -k 10 400 python bench.py --size 768 --vpred --batch 32 --dtype fp8 --steps 2 --warmup 1 --no-cpu-baseline --no-config2 --no-fp8-point --no-driver-points
+step fin_bench_768fp8.log timeout -k 10 400 python bench.py --size 768 --vpred --batch 32 --dtype fp8 --steps 2 --warmup 1
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/fin_bench_default.json").readline())

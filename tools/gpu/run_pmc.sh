@@ -4,7 +4,7 @@ O=$R/gpurun_out/pmc
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 step() { log=$1; shift; "$@" > $O/$log 2>&1; rc=$?; echo "[$log] rc=$rc"; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "timeout/kill: stopping"; tail -n 5 $O/$log; exit $rc; fi; }
-BENCH1="python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-kernel-roofline --no-graph --no-config2 --no-fp8-point --no-driver-points"
+BENCH1="python $R/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-kernel-roofline --no-graph --no-config2 --no-fp8-point --no-driver-points"
 step b1_fetch.log timeout -k 10 500 rocprofv3 --pmc FETCH_SIZE -M --output-format csv -d $O/b1_fetch -- $BENCH1
 step b1_write.log timeout -k 10 500 rocprofv3 --pmc WRITE_SIZE -M --output-format csv -d $O/b1_write -- $BENCH1
 SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT"
