@@ -39,6 +39,53 @@ def _check(out, ref, tol, what=""):
     assert err <= tol * max(1.0, mag), f"{what}: max err {err:.4e} vs tol {tol * max(1.0, mag):.4e} (|ref| max {mag:.3f})"
 
 
+class _Descs:
+    """Collects the descriptors eng.gemm hands to idb_gemm (its launch log), so a test can ask the planner's own queries about them."""
+
+    def __init__(self, eng):
+        self.eng = eng
+
+    def __enter__(self):
+        self.prev, self.eng.launch_log = self.eng.launch_log, []
+        return self.eng.launch_log
+
+    def __exit__(self, *exc):
+        self.eng.launch_log = self.prev
+
+
+def _want_gn(eng, entry, gn_stats=32):
+    """Does eng.gemm attach GroupNorm statistics (out._gn) to this launch?  Exactly when idb_gemm_emits_gn_partials says the plan emits
+    them without an extra launch (engine.gemm's rule)."""
+    import ctypes as C
+    d = entry["desc"]
+    if not (gn_stats and eng._gn_fuse and d.out_h * d.out_w % 64 == 0 and d.out_h * d.out_w <= 4096 and not d.geglu and d.out_dtype == d.dtype
+            and d.n % gn_stats == 0):
+        return False
+    mode = eng.lib.idb_gemm_emits_gn_partials(C.byref(d), gn_stats)
+    return mode == 1 or (mode == 2 and eng._gn_epi)
+
+
+def _want_rs(eng, entry):
+    """Does eng.gemm(row_stats=True) attach row statistics (out._rs)?  Exactly when idb_gemm_row_stats_tiles > 0."""
+    import ctypes as C
+    return eng._ln_fold and eng.lib.idb_gemm_row_stats_tiles(C.byref(entry["desc"])) > 0
+
+
+def _gn_sums(out, b, hw, n, groups=32):
+    """float64 {sum, sum of squares} per (sample, 64-row chunk, group) of the rounded output, and the fp32 summation bound."""
+    x = out.double().reshape(b, hw // 64, 64, groups, n // groups)
+    want = torch.stack([x.sum(dim=(2, 4)), (x * x).sum(dim=(2, 4))], dim=-1)
+    cnt = 64 * (n // groups)
+    bnd = torch.stack([x.abs().sum(dim=(2, 4)), (x * x).sum(dim=(2, 4))], dim=-1) * (2.0 * cnt * 2.0 ** -24)
+    return want, bnd
+
+
+def _check_gn(out, b, hw, n):
+    want, bnd = _gn_sums(out, b, hw, n)
+    got = out._gn[0].double().reshape(want.shape)
+    assert ((got - want).abs() <= bnd).all(), ((got - want).abs() / bnd).max().item()
+
+
 # ---------------------------------------------------------------------------------------------------
 # implicit GEMM
 # ---------------------------------------------------------------------------------------------------
@@ -637,12 +684,16 @@ def test_resnet_conv2_with_shortcut_loader_waves(eng):
     w = _rand((cout, 9 * cout + c1 + c2), 74, (9 * cout) ** -0.5).to(eng.tdt)
     bias = _rand((cout,), 75)
     srcs = [(n2, cout, 9, h, h, 0), (xa, c1, 1, h, h, 0), (xb, c2, 1, h, h, 0)]
-    ref = eng.gemm(srcs, w, cout, b, h, h, bias=bias, tile=16, gn_stats=32)
-    out = eng.gemm(srcs, w, cout, b, h, h, bias=bias, tile=56, gn_stats=32)
+    with _Descs(eng) as log:
+        ref = eng.gemm(srcs, w, cout, b, h, h, bias=bias, tile=16, gn_stats=32)
+        out = eng.gemm(srcs, w, cout, b, h, h, bias=bias, tile=56, gn_stats=32)
     torch.cuda.synchronize()
     assert torch.equal(out, ref)
+    want = [_want_gn(eng, e) for e in log]
+    assert (getattr(ref, "_gn", None) is not None, getattr(out, "_gn", None) is not None) == tuple(want)
     assert (getattr(ref, "_gn", None) is None) == (getattr(out, "_gn", None) is None)
     if getattr(ref, "_gn", None) is not None:
+        _check_gn(ref, b, h * h, cout)
         assert torch.equal(ref._gn[0], out._gn[0])
 
 
@@ -722,15 +773,20 @@ def test_conv_patch_resident_small_tiles_and_split_k(eng, b, h, w_, cin, cout, s
     w = eng.tile_weight(eng._pack_conv(wc))
     bias = _rand((cout,), 153)
     res = _rand((b * h * w_, cout), 154).to(eng.tdt)
-    ref = eng.gemm([(x, cin, 9, h, w_, 0)], w, cout, b, h, w_, bias=bias, residual=res, tile=70 + shape, split_k=split_k, gn_stats=32 if cout % 32 == 0 else 0)
-    out = eng.gemm([(x, cin, 9, h, w_, 0)], w, cout, b, h, w_, bias=bias, residual=res, tile=100 + shape, split_k=split_k, gn_stats=32 if cout % 32 == 0 else 0)
+    gs = 32 if cout % 32 == 0 else 0
+    with _Descs(eng) as log:
+        ref = eng.gemm([(x, cin, 9, h, w_, 0)], w, cout, b, h, w_, bias=bias, residual=res, tile=70 + shape, split_k=split_k, gn_stats=gs)
+        out = eng.gemm([(x, cin, 9, h, w_, 0)], w, cout, b, h, w_, bias=bias, residual=res, tile=100 + shape, split_k=split_k, gn_stats=gs)
     torch.cuda.synchronize()
     want = F.conv2d(x.float().permute(0, 3, 1, 2), wc.to(eng.tdt).float(), bias, padding=1).permute(0, 2, 3, 1).reshape(-1, cout) + res.float()
     _check(out, want, _tol(eng), "patch conv, small tile")
     ulp = 2.0 ** (-10 if eng.tdt == torch.float16 else -7)
     assert (out.float() - ref.float()).abs().max().item() <= 2 * ulp * max(1.0, want.abs().max().item())
+    assert (getattr(ref, "_gn", None) is not None, getattr(out, "_gn", None) is not None) == tuple(_want_gn(eng, e, gs) for e in log)
     assert (getattr(ref, "_gn", None) is None) == (getattr(out, "_gn", None) is None)
     if getattr(ref, "_gn", None) is not None:
+        _check_gn(ref, b, h * w_, cout)
+        _check_gn(out, b, h * w_, cout)
         assert torch.allclose(ref._gn[0], out._gn[0], rtol=2e-3, atol=0.5)
 
 
@@ -856,12 +912,15 @@ def test_fused_groupnorm_over_skip_concat_and_shortcut(eng):
     h1 = _rand((b, h, h, cout), 116, 1.3).to(eng.tdt)
     w2 = eng.tile_weight(torch.cat([eng._pack_conv(_rand((cout, cout, 3, 3), 117, (9 * cout) ** -0.5)),
                                     eng._pack_mat(_rand((cout, ca + cb), 118, (ca + cb) ** -0.5))], dim=1).contiguous())
-    ref, fused = _gn_ref_and_fused(eng, [(h1, cout, 9), (xa, ca, 1), (xb, cb, 1)], cout, 1, w2, cout, b, h, h, 76, True, 1e-5, 119,
-                                   extra=dict(bias=bias, gn_stats=32))
+    with _Descs(eng) as log:
+        ref, fused = _gn_ref_and_fused(eng, [(h1, cout, 9), (xa, ca, 1), (xb, cb, 1)], cout, 1, w2, cout, b, h, h, 76, True, 1e-5, 119,
+                                       extra=dict(bias=bias, gn_stats=32))
     assert torch.equal(fused, ref)
     # (the statistics of the output are summed by 256 threads here and 512 in the unfused kernel: same values, different order)
+    assert (getattr(ref, "_gn", None) is not None, getattr(fused, "_gn", None) is not None) == tuple(_want_gn(eng, e) for e in log)
     assert (getattr(fused, "_gn", None) is None) == (getattr(ref, "_gn", None) is None)
     if getattr(fused, "_gn", None) is not None:
+        _check_gn(fused, b, h * h, cout)
         assert torch.allclose(fused._gn[0], ref._gn[0], rtol=1e-5, atol=1e-2)
 
 
@@ -879,12 +938,17 @@ def test_fused_groupnorm_silu_in_patch_resident_conv_bit_identical(eng, b, h, ci
                                        extra=dict(bias=bias, sbias=(sb, 0, cout), residual=res, gn_stats=32 if cout % 32 == 0 else 0),
                                        split_k=split_k, ref_tile=100 + shape)
         assert torch.equal(fused, ref)
-    # the auto plan takes the same kernel when a GroupNorm is handed in
+    # the auto plan takes the same kernel when a GroupNorm is handed in — exactly when idb_gemm_fuses_groupnorm says so; otherwise
+    # idb_gemm refuses the descriptor before any launch
     if eng.fuses_groupnorm([(cin, 9)], w, cout, b, h, h, 32, 1):
         auto = eng.gemm([(x, cin, 9, h, h, 0)], w, cout, b, h, h, bias=bias, sbias=(sb, 0, cout), residual=res,
                         gn_in=_last_gn_in(eng, x, cin, b, h, False, 166))
         torch.cuda.synchronize()
         assert (auto.float() - ref.float()).abs().max().item() <= 4 * _tol(eng) * max(1.0, ref.float().abs().max().item())
+    else:
+        with pytest.raises(RuntimeError, match="status -2"):
+            eng.gemm([(x, cin, 9, h, h, 0)], w, cout, b, h, h, bias=bias, sbias=(sb, 0, cout), residual=res,
+                     gn_in=_last_gn_in(eng, x, cin, b, h, False, 166))
 
 
 def _last_gn_in(eng, x, cin, b, h, silu, seed):
@@ -916,7 +980,13 @@ def test_fused_groupnorm_proj_in_no_silu_with_row_stats(eng):
     x = _rand((b, h, h, c), 121, 2.0).to(eng.tdt)
     w = eng.tile_weight(eng._pack_mat(_rand((c, c), 122, c ** -0.5)))
     bias = _rand((c,), 123)
-    ref, fused = _gn_ref_and_fused(eng, [(x, c, 1)], c, 1, w, c, b, h, h, 56, False, 1e-6, 124, extra=dict(bias=bias, row_stats=True))
+    with _Descs(eng) as log:
+        ref, fused = _gn_ref_and_fused(eng, [(x, c, 1)], c, 1, w, c, b, h, h, 56, False, 1e-6, 124, extra=dict(bias=bias, row_stats=True))
     assert torch.equal(fused, ref)
+    assert (getattr(ref, "_rs", None) is not None, getattr(fused, "_rs", None) is not None) == tuple(_want_rs(eng, e) for e in log)
     if getattr(ref, "_rs", None) is not None:       # row statistics: summed by 4 threads per row here, 8 in the 8-wave kernel (same values, other order)
         assert getattr(fused, "_rs", None) is not None and torch.allclose(fused._rs[0], ref._rs[0], rtol=1e-5, atol=1e-2)
+        nt = ref._rs[1]
+        xr = ref.double().reshape(b * h * h, nt, -1)
+        rs = ref._rs[0].double().reshape(b * h * h, nt, 2)
+        assert torch.allclose(rs[..., 0], xr.sum(-1), rtol=1e-5, atol=1e-3) and torch.allclose(rs[..., 1], (xr * xr).sum(-1), rtol=1e-5, atol=1e-3)
