@@ -252,7 +252,47 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const T* __restrict__ q, 
     }
 }
 
+// The kernel form for a problem: the one decision both idb_attention (the launch) and idb_attention_plan (the host-only query) read.
+struct AttnPlan {
+    int waves, key_split, rows;   // waves per workgroup (2 / 4 / 8 / 12); 1 or 2 waves per query row; query rows per workgroup
+    dim3 grid;
+};
+
+AttnPlan attn_plan(int batch, int heads, int n_q, int n_kv, int causal) {
+    // 64-row blocks only when 128-row blocks would leave half the CUs idle (measured: slower otherwise)
+    const long long blocks128 = (long long)((n_q + 127) / 128) * heads * batch;
+    const bool small = blocks128 < 128;
+    // about one 128-row workgroup per CU and a long key sweep: 8 waves, key halves split between wave pairs (attn_kernel)
+    static const int env_ks = [] { const char* e = getenv("IDB_ATTN_KSPLIT"); return e ? atoi(e) : 1; }();
+    // (on larger grids the 8-wave form loses: batch 64 15.44 -> 15.22 images/s, batch 8 14.16 -> 13.96 with it everywhere)
+    const bool ksplit = env_ks && !small && !causal && blocks128 < 512 && n_kv >= 512;
+    // 257-511 workgroups of 128 rows = two uneven rounds (the CUs that get two set the time): 192-row workgroups (12 waves, three
+    // per SIMD) when that grid fits one round — the 64x64 level at batch 1: 320 -> 220 workgroups
+    const long long blocks192 = (long long)((n_q + 191) / 192) * heads * batch;
+    const bool wide = ksplit && env_ks != 2 && blocks128 > 256 && blocks192 <= 256;
+    AttnPlan p;
+    p.waves = small ? 2 : !ksplit ? 4 : wide ? 12 : 8;
+    p.key_split = ksplit ? 2 : 1;
+    p.rows = 32 * p.waves / p.key_split;
+    p.grid = dim3((n_q + p.rows - 1) / p.rows, heads, batch);
+    return p;
+}
+
 }  // namespace
+
+extern "C" int idb_attention_plan(int32_t batch, int32_t heads, int32_t n_q, int32_t n_kv, int32_t causal, int32_t* waves,
+                                  int32_t* key_split, int32_t* rows, int32_t* blocks) {
+    IDB_REQUIRE(waves && key_split && rows && blocks, "idb_attention_plan: null pointer");
+    IDB_REQUIRE(batch > 0 && heads > 0 && n_q > 0 && n_kv > 0, "idb_attention_plan: bad dims");
+    IDB_REQUIRE(batch <= 65535 && heads <= 65535, "idb_attention_plan: grid too large");
+    IDB_REQUIRE(!causal || n_q == n_kv, "idb_attention_plan: causal needs n_q == n_kv");
+    const AttnPlan p = attn_plan(batch, heads, n_q, n_kv, causal);
+    *waves = p.waves;
+    *key_split = p.key_split;
+    *rows = p.rows;
+    *blocks = (int32_t)(p.grid.x * p.grid.y * p.grid.z);
+    return IDB_OK;
+}
 
 extern "C" int idb_attention(const void* q, int32_t q_ld, const void* k, const void* v, int32_t kv_ld, void* out,
                              int32_t out_ld, int32_t batch, int32_t heads, int32_t n_q, int32_t n_kv, int32_t n_kv_alloc,
@@ -267,18 +307,9 @@ extern "C" int idb_attention(const void* q, int32_t q_ld, const void* k, const v
     IDB_REQUIRE(!causal || n_q == n_kv, "idb_attention: causal needs n_q == n_kv");
     const float sl2 = scale * 1.44269504088896340736f;
     hipStream_t st = (hipStream_t)stream;
-    // 64-row blocks only when 128-row blocks would leave half the CUs idle (measured: slower otherwise)
-    const long long blocks128 = (long long)((n_q + 127) / 128) * heads * batch;
-    const bool small = blocks128 < 128;
-    // about one 128-row workgroup per CU and a long key sweep: 8 waves, key halves split between wave pairs (attn_kernel)
-    static const int env_ks = [] { const char* e = getenv("IDB_ATTN_KSPLIT"); return e ? atoi(e) : 1; }();
-    // (on larger grids the 8-wave form loses: batch 64 15.44 -> 15.22 images/s, batch 8 14.16 -> 13.96 with it everywhere)
-    const bool ksplit = env_ks && !small && !causal && blocks128 < 512 && n_kv >= 512;
-    // 257-511 workgroups of 128 rows = two uneven rounds (the CUs that get two set the time): 192-row workgroups (12 waves, three
-    // per SIMD) when that grid fits one round — the 64x64 level at batch 1: 320 -> 220 workgroups
-    const long long blocks192 = (long long)((n_q + 191) / 192) * heads * batch;
-    const bool wide = ksplit && env_ks != 2 && blocks128 > 256 && blocks192 <= 256;
-    const dim3 grid(wide ? (n_q + 191) / 192 : (n_q + (small ? 63 : 127)) / (small ? 64 : 128), heads, batch);
+    const AttnPlan plan = attn_plan(batch, heads, n_q, n_kv, causal);
+    const dim3 grid = plan.grid;
+    const bool small = plan.waves == 2, ksplit = plan.key_split == 2, wide = plan.waves == 12;
 #define IDB_ATTN_LAUNCH(T, NW)                                                                                          \
     hipLaunchKernelGGL((attn_kernel<T, NW>), grid, dim3(64 * NW), 0, st, (const T*)q, q_ld, (const T*)k, (const T*)v, kv_ld, \
                        (T*)out, out_ld, n_q, n_kv, n_kv_alloc, sl2, causal)

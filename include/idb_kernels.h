@@ -245,6 +245,11 @@ int idb_attention(const void* q, int32_t q_ld, const void* k, const void* v, int
                   void* out, int32_t out_ld, int32_t batch, int32_t heads, int32_t n_q, int32_t n_kv,
                   int32_t n_kv_alloc, float scale, int32_t causal, int32_t dtype, void* stream);
 /* causal != 0: query i attends keys 0..i only (CLIPTextModel's causal mask, n_q == n_kv). */
+/* Host-only: the kernel form idb_attention would launch for these arguments (same validation of the dims, no HIP
+ * call).  waves: 2, 4, 8 or 12 per workgroup; key_split: 1 or 2; rows: query rows per workgroup (64/128/192);
+ * blocks: workgroups in the grid. */
+int idb_attention_plan(int32_t batch, int32_t heads, int32_t n_q, int32_t n_kv, int32_t causal,
+                       int32_t* waves, int32_t* key_split, int32_t* rows, int32_t* blocks);
 
 /* Token + position embedding gather of CLIPTextModel: out[b][t][:] = tok[ids[b][t]][:] + pos[t][:]
  * (fp32 tables, operand-dtype output).  ids are int64 on the device; out-of-range ids are an error the

@@ -29,6 +29,16 @@ def _tol(eng):
     return 2.0 ** -7 if eng.dtype_name == "bf16" else 2.0 ** -9
 
 
+def test_causal_attention_shapes_form(eng):
+    """All four shapes of test_causal_attention run the 2-wave 64-row form (idb_attention_plan); the 4-wave causal sweep is covered by
+    tests/test_attn_matrix_gpu.py."""
+    import ctypes as C
+    for b, heads, n in [(2, 16, 77), (3, 2, 77), (1, 4, 200), (2, 1, 64)]:
+        o = [C.c_int32(-1) for _ in range(4)]
+        assert eng.lib.idb_attention_plan(b, heads, n, n, 1, *[C.byref(x) for x in o]) == 0
+        assert o[0].value == 2, (b, heads, n, o[0].value)
+
+
 @pytest.mark.parametrize("b,heads,n", [(2, 16, 77), (3, 2, 77), (1, 4, 200), (2, 1, 64)])
 def test_causal_attention(eng, b, heads, n):
     c = heads * 64

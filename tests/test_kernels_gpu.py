@@ -374,6 +374,24 @@ def test_softmax_rows(eng):
 # ---------------------------------------------------------------------------------------------------
 # (2,10,1024), (3,7,1000): grids of 128-256 workgroups -> the 8-wave key-split form (wave pairs merge through LDS);
 # (2,5,4096), (2,11,1600): 257-511 workgroups of 128 rows -> the 12-wave 192-row form
+def _form(eng, b, heads, n_q, n_kv, causal=False):
+    """Waves per workgroup of the kernel form idb_attention launches for this problem (idb_attention_plan)."""
+    import ctypes as C
+    o = [C.c_int32(-1) for _ in range(4)]
+    assert eng.lib.idb_attention_plan(b, heads, n_q, n_kv, int(causal), *[C.byref(x) for x in o]) == 0
+    return o[0].value
+
+
+def test_attention_shapes_reach_every_form(eng):
+    """The shape lists below still cover the forms their comments name."""
+    assert [_form(eng, b, h, n, n) for b, h, n in [(2, 10, 1024), (3, 7, 1000)]] == [8, 8]
+    assert [_form(eng, b, h, n, n) for b, h, n in [(2, 5, 4096), (2, 11, 1600)]] == [12, 12]
+    assert {_form(eng, b, h, n, n) for b, h, n in [(2, 5, 1024), (1, 2, 4096), (3, 4, 64), (2, 20, 256), (1, 3, 144)]} == {2}
+    assert [_form(eng, 1, 2, 512, 512), _form(eng, 2, 10, 1024, 1024)] == [2, 8]                  # test_attention_peaked_softmax
+    assert [_form(eng, 2, 10, 1024, n) for n in (77, 600, 545)] == [4, 8, 8]                      # test_cross_attention
+    assert {_form(eng, b, h, n, c) for b, h, n, c in [(2, 5, 1024, 77), (2, 20, 64, 77), (1, 10, 256, 64), (1, 1, 128, 130)]} == {2}
+
+
 @pytest.mark.parametrize("b,heads,n", [(2, 5, 1024), (1, 2, 4096), (3, 4, 64), (2, 20, 256), (1, 3, 144), (2, 5, 4096), (2, 10, 1024), (3, 7, 1000), (2, 11, 1600)])
 def test_self_attention(eng, b, heads, n):
     c = heads * 64
