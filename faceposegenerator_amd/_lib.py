@@ -21,7 +21,7 @@ EXPORTS = [
     "idb_version", "idb_launch_count", "idb_last_error", "idb_device_check",
     "idb_gemm_workspace_bytes", "idb_gemm_plan", "idb_gemm_row_stats_tiles", "idb_gemm_folds_layernorm", "idb_gemm_fuses_groupnorm", "idb_gemm_emits_gn_partials", "idb_gemm",
     "idb_pack_conv_weight", "idb_pack_matrix", "idb_tiled_weight_bytes", "idb_tile_weight", "idb_lora_merge", "idb_lora_merge_scaled", "idb_pack_matrix_scaled", "idb_ln_fold_vectors",
-    "idb_groupnorm_workspace_bytes", "idb_groupnorm", "idb_layernorm", "idb_groupnorm_stats",
+    "idb_groupnorm_workspace_bytes", "idb_groupnorm", "idb_groupnorm_plan", "idb_layernorm", "idb_groupnorm_stats",
     "idb_attention", "idb_attention_plan", "idb_embed_tokens", "idb_softmax_rows",
     "idb_timestep_sinusoid", "idb_linear_f32", "idb_conv_in",
     "idb_cfg_ddpm_step", "idb_postprocess",
@@ -105,6 +105,7 @@ def load() -> C.CDLL:
         "idb_lora_merge": (C.c_int, [vp, vp, vp, vp, i64, i64, i32, f32, i32, vp]),
         "idb_groupnorm_workspace_bytes": (sz, [i32, i32, i32]),
         "idb_groupnorm": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, i32, vp, sz, vp, i32, vp, i32, vp]),
+        "idb_groupnorm_plan": (C.c_int, [i32] * 7 + [C.POINTER(i32)] * 7),
         "idb_layernorm": (C.c_int, [vp, vp, i64, i32, f32, vp, vp, i32, vp]),
         "idb_groupnorm_stats": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, vp, sz, C.POINTER(i32), i32, vp]),
         "idb_attention": (C.c_int, [vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp]),

@@ -42,7 +42,8 @@ inline GnGeom gn_geometry(int c0, int c1, int batch, int hw, int groups) {
     g.SW = sw; g.cols = sw / 8; g.PR = GN_THREADS / g.cols; g.nslices = g.C / sw; g.gps = sw / g.cpg;
     // enough pixel chunks that the grid has >= ~1024 workgroups, each with >= 2 pixels per thread row
     int want = (1024 + batch * g.nslices - 1) / (batch * g.nslices);
-    int by_hw = (hw + 2 * g.PR - 1) / (2 * g.PR);
+    const int pr2 = 2 * (g.PR > 0 ? g.PR : 1);                   // PR == 0: more than GN_THREADS vector columns, refused by every caller
+    int by_hw = (hw + pr2 - 1) / pr2;
     int n = want < by_hw ? want : by_hw;
     if (n < 1) n = 1;
     if (n > GN_MAXCHUNKS) n = GN_MAXCHUNKS;
@@ -485,53 +486,88 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(T* x, int cols) {
     }
 }
 
+// What one GroupNorm call launches: the one decision both run_groupnorm (the launch) and idb_groupnorm_plan (the host-only query)
+// read.  form 0: gn_stats_kernel + gn_apply_kernel; 1: gn_sync_kernel; 2: gn_apply_kernel alone on the caller's partials.  g carries
+// the pixel chunks of that form; ppb / apply_blocks are the pixels per workgroup and the grid.x of gn_apply_kernel (0: not launched).
+struct GnPlan {
+    int form;
+    GnGeom g;
+    int ppb, apply_blocks;
+};
+
+// sync_len: length of the caller's hand-off counter array, 0 without one; pin_chunks: partials_chunks of partials_in, 0 without.
+inline GnPlan gn_plan(int c0, int c1, int batch, int hw, int groups, int sync_len, int pin_chunks) {
+    GnPlan p;
+    p.g = gn_geometry(c0, c1, batch, hw, groups);
+    const GnGeom& g = p.g;
+    const int want = (2048 + batch * g.nslices - 1) / (batch * g.nslices);
+    p.ppb = (hw + want - 1) / want;
+    if (p.ppb < g.PR * 2) p.ppb = g.PR * 2;
+    p.apply_blocks = (hw + p.ppb - 1) / p.ppb;
+    if (pin_chunks > 0) {                        // statistics came with the tensor (idb_gemm_desc.gn_partials): normalise only
+        p.form = 2;
+        p.g.nchunks = pin_chunks;
+        p.g.chunk_len = 64;
+        return p;
+    }
+    // single launch when the caller passes hand-off counters and every workgroup of the grid is resident at once (see
+    // gn_sync_kernel).  Measured in the sampling loop (batch 1, A/B on one box): 6.05 images/s against 6.28 for the
+    // two-launch form — the hand-off is four dependent agent-scope round trips (publish, arrive, poll, read partials),
+    // dearer on this chip than a second launch (1.8 us floor inside a graph); the engine therefore passes no counters
+    // unless IDB_GN_SYNC=1.  A one-workgroup-per-(sample, slice) form that keeps feature maps up to 32x32 in registers
+    // (one launch, one read) measured equal to the two-launch form (6.285 vs 6.284: 32-64 workgroups cannot pull their
+    // slices faster than 512 can pull them twice) and was dropped.
+    GnGeom f = g;
+    f.nchunks = (hw + GN_SYNC_MAXIT * f.PR - 1) / (GN_SYNC_MAXIT * f.PR);
+    f.chunk_len = (hw + f.nchunks - 1) / f.nchunks;
+    const long long blocks = (long long)f.nchunks * f.nslices * batch;
+    if (sync_len > 0 && f.nchunks <= GN_MAXCHUNKS && blocks <= GN_SYNC_MAXBLOCKS && 2LL * batch * f.nslices <= sync_len &&
+        (f.chunk_len + f.PR - 1) / f.PR <= GN_SYNC_MAXIT) {
+        p.form = 1;
+        p.g = f;
+        p.apply_blocks = 0;
+        return p;
+    }
+    p.form = 0;
+    return p;
+}
+
 template <typename T>
 int run_groupnorm(const void* x0, int c0, const void* x1, int c1, int batch, int hw, int groups, float eps,
                   const float* gamma, const float* beta, int silu, void* out, void* ws, int* sync, int sync_len, const float* pin,
                   int pin_chunks, hipStream_t st, float out8 = 0.f) {
-    GnGeom g = gn_geometry(c0, c1, batch, hw, groups);
-    if (pin) {                                   // statistics came with the tensor (idb_gemm_desc.gn_partials): normalise only
-        g.nchunks = pin_chunks;
-        g.chunk_len = 64;
-        int want = (2048 + batch * g.nslices - 1) / (batch * g.nslices);
-        int ppb = (hw + want - 1) / want;
-        if (ppb < g.PR * 2) ppb = g.PR * 2;
-        const int nblk = (hw + ppb - 1) / ppb;
-        hipLaunchKernelGGL((gn_apply_kernel<T>), dim3(nblk, g.nslices, batch), dim3(GN_THREADS), 0, st, (const T*)x0, (const T*)x1, g,
-                           pin, gamma, beta, eps, silu, (T*)out, ppb, out8);
+    const GnPlan p = gn_plan(c0, c1, batch, hw, groups, sync ? sync_len : 0, pin ? pin_chunks : 0);
+    const GnGeom& g = p.g;
+    if (p.form == 2) {
+        hipLaunchKernelGGL((gn_apply_kernel<T>), dim3(p.apply_blocks, g.nslices, batch), dim3(GN_THREADS), 0, st, (const T*)x0, (const T*)x1, g,
+                           pin, gamma, beta, eps, silu, (T*)out, p.ppb, out8);
         IDB_CHECK_LAUNCH("idb_groupnorm(apply)");
         return IDB_OK;
     }
-    {
-        // single launch when the caller passes hand-off counters and every workgroup of the grid is resident at once (see
-        // gn_sync_kernel).  Measured in the sampling loop (batch 1, A/B on one box): 6.05 images/s against 6.28 for the
-        // two-launch form — the hand-off is four dependent agent-scope round trips (publish, arrive, poll, read partials),
-        // dearer on this chip than a second launch (1.8 us floor inside a graph); the engine therefore passes no counters
-        // unless IDB_GN_SYNC=1.  A one-workgroup-per-(sample, slice) form that keeps feature maps up to 32x32 in registers
-        // (one launch, one read) measured equal to the two-launch form (6.285 vs 6.284: 32-64 workgroups cannot pull their
-        // slices faster than 512 can pull them twice) and was dropped.
-        GnGeom f = g;
-        f.nchunks = (hw + GN_SYNC_MAXIT * f.PR - 1) / (GN_SYNC_MAXIT * f.PR);
-        f.chunk_len = (hw + f.nchunks - 1) / f.nchunks;
-        const long long blocks = (long long)f.nchunks * f.nslices * batch;
-        if (sync && f.nchunks <= GN_MAXCHUNKS && blocks <= GN_SYNC_MAXBLOCKS && 2LL * batch * f.nslices <= sync_len &&
-            (f.chunk_len + f.PR - 1) / f.PR <= GN_SYNC_MAXIT) {
-            hipLaunchKernelGGL((gn_sync_kernel<T>), dim3(f.nchunks, f.nslices, batch), dim3(GN_THREADS), 0, st, (const T*)x0,
-                               (const T*)x1, f, (float*)ws, sync, gamma, beta, eps, silu, (T*)out);
-            IDB_CHECK_LAUNCH("idb_groupnorm(sync)");
-            return IDB_OK;
-        }
+    if (p.form == 1) {
+        hipLaunchKernelGGL((gn_sync_kernel<T>), dim3(g.nchunks, g.nslices, batch), dim3(GN_THREADS), 0, st, (const T*)x0,
+                           (const T*)x1, g, (float*)ws, sync, gamma, beta, eps, silu, (T*)out);
+        IDB_CHECK_LAUNCH("idb_groupnorm(sync)");
+        return IDB_OK;
     }
     hipLaunchKernelGGL((gn_stats_kernel<T>), dim3(g.nchunks, g.nslices, batch), dim3(GN_THREADS), 0, st, (const T*)x0,
                        (const T*)x1, g, (float*)ws);
     IDB_CHECK_LAUNCH("idb_groupnorm(stats)");
-    int want = (2048 + batch * g.nslices - 1) / (batch * g.nslices);
-    int ppb = (hw + want - 1) / want;
-    if (ppb < g.PR * 2) ppb = g.PR * 2;
-    const int nblk = (hw + ppb - 1) / ppb;
-    hipLaunchKernelGGL((gn_apply_kernel<T>), dim3(nblk, g.nslices, batch), dim3(GN_THREADS), 0, st, (const T*)x0,
-                       (const T*)x1, g, (const float*)ws, gamma, beta, eps, silu, (T*)out, ppb, out8);
+    hipLaunchKernelGGL((gn_apply_kernel<T>), dim3(p.apply_blocks, g.nslices, batch), dim3(GN_THREADS), 0, st, (const T*)x0,
+                       (const T*)x1, g, (const float*)ws, gamma, beta, eps, silu, (T*)out, p.ppb, out8);
     IDB_CHECK_LAUNCH("idb_groupnorm(apply)");
+    return IDB_OK;
+}
+
+// The dimension checks idb_groupnorm and idb_groupnorm_plan share (who: the entry point's name, for the message).
+static int gn_check_dims(const char* who, int c0, int c1, int batch, int hw, int groups) {
+    IDB_REQUIRE(batch > 0 && hw > 0 && groups > 0 && c0 > 0 && c1 >= 0, "%s: bad dims", who);
+    const int C = c0 + c1;
+    IDB_REQUIRE(c0 % 8 == 0 && c1 % 8 == 0 && C % groups == 0, "%s: channels %d+%d / groups %d unsupported", who, c0, c1, groups);
+    IDB_REQUIRE(C / groups >= 2, "%s: needs at least 2 channels per group", who);
+    const GnGeom g = gn_geometry(c0, c1, batch, hw, groups);
+    IDB_REQUIRE(g.cols <= GN_THREADS && g.gps <= 64 && batch <= 65535 && g.nslices <= 65535,
+                "%s: unsupported geometry C=%d groups=%d (slice %d channels, %d groups/slice)", who, C, groups, g.SW, g.gps);
     return IDB_OK;
 }
 
@@ -541,7 +577,7 @@ int idb_launch_gn_stats64(const void* x, int c, int batch, int hw, int groups, f
     IDB_REQUIRE(x && partial && hw % 64 == 0 && hw / 64 <= GN_MAXCHUNKS && c % 8 == 0 && c % groups == 0 && c / groups >= 2,
                 "idb_gemm: gn_partials unsupported for hw=%d c=%d groups=%d", hw, c, groups);
     GnGeom g = gn_geometry(c, 0, batch, hw, groups);
-    IDB_REQUIRE(g.cols <= GN_THREADS && g.gps <= 64, "idb_gemm: gn_partials unsupported geometry");
+    IDB_REQUIRE(g.cols <= GN_THREADS && g.gps <= 64 && batch <= 65535 && g.nslices <= 65535, "idb_gemm: gn_partials unsupported geometry");
     g.nchunks = hw / 64;
     g.chunk_len = 64;
     if (dtype == IDB_BF16)
@@ -561,7 +597,7 @@ extern "C" int idb_groupnorm_stats(const void* x0, int32_t c0, const void* x1, i
     IDB_REQUIRE(c0 > 0 && c0 % 8 == 0 && c1 % 8 == 0 && (x1 != nullptr) == (c1 > 0) && (c0 + c1) % groups == 0 && (c0 + c1) / groups >= 2,
                 "idb_groupnorm_stats: c0=%d c1=%d groups=%d unsupported", c0, c1, groups);
     const GnGeom g = gn_geometry(c0, c1, batch, hw, groups);
-    IDB_REQUIRE(g.cols <= GN_THREADS && g.gps <= 64, "idb_groupnorm_stats: unsupported geometry");
+    IDB_REQUIRE(g.cols <= GN_THREADS && g.gps <= 64 && batch <= 65535 && g.nslices <= 65535, "idb_groupnorm_stats: unsupported geometry");
     IDB_REQUIRE(partials_bytes >= (size_t)batch * g.nchunks * groups * 2 * sizeof(float), "idb_groupnorm_stats: partials buffer too small");
     hipStream_t st = (hipStream_t)stream;
     if (dtype == IDB_BF16)
@@ -588,14 +624,7 @@ extern "C" int idb_groupnorm(const void* x0, int32_t c0, const void* x1, int32_t
     IDB_REQUIRE(batch > 0 && hw > 0 && groups > 0 && c0 > 0 && c1 >= 0, "idb_groupnorm: bad dims");
     IDB_REQUIRE((c1 == 0) == (x1 == nullptr), "idb_groupnorm: x1/c1 mismatch");
     IDB_REQUIRE(c1 == 0 || idb_aligned16(x1), "idb_groupnorm: x1 unaligned");
-    const int C = c0 + c1;
-    IDB_REQUIRE(c0 % 8 == 0 && c1 % 8 == 0 && C % groups == 0, "idb_groupnorm: channels %d+%d / groups %d unsupported", c0, c1, groups);
-    IDB_REQUIRE(C / groups >= 2, "idb_groupnorm: needs at least 2 channels per group");
-    {
-        const GnGeom g = gn_geometry(c0, c1, batch, hw, groups);
-        IDB_REQUIRE(g.cols <= GN_THREADS && g.gps <= 64 && batch <= 65535 && g.nslices <= 65535,
-                    "idb_groupnorm: unsupported geometry C=%d groups=%d (slice %d channels, %d groups/slice)", C, groups, g.SW, g.gps);
-    }
+    if (const int rc = gn_check_dims("idb_groupnorm", c0, c1, batch, hw, groups)) return rc;
     const size_t need = idb_groupnorm_workspace_bytes(batch, hw, groups);
     IDB_REQUIRE(workspace && workspace_bytes >= need, "idb_groupnorm: workspace too small (%zu < %zu)", workspace_bytes, need);
     IDB_REQUIRE(!sync || (sync_len > 0 && ((uintptr_t)sync & 3) == 0), "idb_groupnorm: bad sync counter array");
@@ -608,6 +637,25 @@ extern "C" int idb_groupnorm(const void* x0, int32_t c0, const void* x1, int32_t
                                        partials_chunks, st)
                : run_groupnorm<_Float16>(x0, c0, x1, c1, batch, hw, groups, eps, gamma, beta, silu, out, workspace, sync, sync_len, partials_in,
                                          partials_chunks, st);
+}
+
+extern "C" int idb_groupnorm_plan(int32_t c0, int32_t c1, int32_t batch, int32_t hw, int32_t groups, int32_t sync_len, int32_t partials_chunks,
+                                  int32_t* form, int32_t* slice_channels, int32_t* slices, int32_t* chunks, int32_t* chunk_len,
+                                  int32_t* rows_per_pass, int32_t* apply_blocks) {
+    IDB_REQUIRE(form && slice_channels && slices && chunks && chunk_len && rows_per_pass && apply_blocks, "idb_groupnorm_plan: null pointer");
+    if (const int rc = gn_check_dims("idb_groupnorm_plan", c0, c1, batch, hw, groups)) return rc;
+    IDB_REQUIRE(sync_len >= 0, "idb_groupnorm_plan: bad sync counter array");
+    IDB_REQUIRE(partials_chunks == 0 || (c1 == 0 && hw % 64 == 0 && partials_chunks == hw / 64 && partials_chunks <= GN_MAXCHUNKS),
+                "idb_groupnorm_plan: partials_in needs one dense input, hw %% 64 == 0, partials_chunks == hw / 64 <= %d", GN_MAXCHUNKS);
+    const GnPlan p = gn_plan(c0, c1, batch, hw, groups, sync_len, partials_chunks);
+    *form = p.form;
+    *slice_channels = p.g.SW;
+    *slices = p.g.nslices;
+    *chunks = p.g.nchunks;
+    *chunk_len = p.g.chunk_len;
+    *rows_per_pass = p.g.PR;
+    *apply_blocks = p.apply_blocks;
+    return IDB_OK;
 }
 
 extern "C" int idb_groupnorm_fp8(const void* x0, int32_t c0, const void* x1, int32_t c1, int32_t batch, int32_t hw, int32_t groups, float eps,

@@ -213,8 +213,12 @@ int idb_ln_fold_vectors(const float* w, const float* lora_a, const float* lora_b
  * Replaces nn.GroupNorm(32, C) (+ SiLU) of ResnetBlock2D / Transformer2DModel.norm / conv_norm_out
  * and nn.LayerNorm(C) x3 of BasicTransformerBlock.
  * GroupNorm input may be the channel-concatenation of two NHWC tensors (skip connections); the
- * output is one dense [B][HW][C0+C1] tensor.  Statistics are fp32, deterministic (fixed summation
- * order; no float atomics).
+ * output is one dense [B][HW][C0+C1] tensor.  Statistics are one-pass fp32 ({sum, sum of squares}; var = E[x^2] - mean^2 formed in
+ * double), deterministic (fixed summation order; no float atomics).  Measured on MI355X against float64 (tests/test_norm_matrix_gpu.py),
+ * outputs of magnitude >= 1: within one output ulp of nn.GroupNorm for |mean| / std up to 256 in bf16 (worst 0.76 ulp at 1 Mi elements
+ * per group) and up to 16 in f16 (0.53 ulp at 1 Mi elements per group); f16 at |mean| / std = 64 is off by 0.8 / 0.9 / 1.3 ulp and at 256
+ * by 4 / 9 / 19 ulp for 2560 / 40960 / 1 Mi elements per group.  The error of the mean is absolute, so relative to outputs near zero no
+ * bound holds at any conditioning.
  * sync: optional array of sync_len int32 counters that is ZERO on first use (the kernel leaves it
  * zero): when given, and the whole grid is resident on the chip at once (small batches), the two
  * passes run as ONE launch whose workgroups hand their partial sums over through these counters;
@@ -229,6 +233,15 @@ int idb_groupnorm(const void* x0, int32_t c0, const void* x1, int32_t c1, int32_
                   int32_t sync_len, const float* partials_in, int32_t partials_chunks, void* stream);
 int idb_layernorm(const void* x, void* out, int64_t rows, int32_t c, float eps, const float* gamma,
                   const float* beta, int32_t dtype, void* stream);
+/* Host-only: what idb_groupnorm would launch for these arguments (same validation of the dims, no HIP call).  sync_len: length of
+ * the hand-off counter array, 0 without one; partials_chunks: 0 without partials_in.  form: 0 two launches (statistics, normalise),
+ * 1 single launch with hand-off, 2 normalise only (partials_in); slice_channels x slices = C0 + C1: the channel slice one workgroup
+ * owns; chunks x chunk_len >= hw: the pixel chunks of the statistics ([batch][chunks][groups][2] partials; idb_groupnorm_stats
+ * reports the chunks of form 0); rows_per_pass: pixels one workgroup covers per step (256 / (slice_channels / 8));
+ * apply_blocks: pixel blocks of the normalise launch (0 in form 1).  idb_groupnorm_fp8 launches what sync_len = 0 reports. */
+int idb_groupnorm_plan(int32_t c0, int32_t c1, int32_t batch, int32_t hw, int32_t groups, int32_t sync_len, int32_t partials_chunks,
+                       int32_t* form, int32_t* slice_channels, int32_t* slices, int32_t* chunks, int32_t* chunk_len,
+                       int32_t* rows_per_pass, int32_t* apply_blocks);
 /* First GroupNorm pass only: partial {sum, sum of squares} per (sample, pixel chunk, group) of the channel concatenation x0 | x1,
  * fp32 [batch][*chunks][groups][2] in `partials` (capacity: idb_groupnorm_workspace_bytes) — for callers that
  * want the statistics of a tensor whose producer did not emit them (skip concatenations, conv_in).  *chunks receives the pixel-chunk count (<= 64). */

@@ -254,11 +254,27 @@ def test_gemm_rejects_bad_args(eng):
 # ---------------------------------------------------------------------------------------------------
 # norms / softmax
 # ---------------------------------------------------------------------------------------------------
+def _gn_plan(eng, c0, c1, b, hw, sync_len=0, groups=32):
+    """(form, slice channels, chunks, chunk length, rows per pass) idb_groupnorm would launch (idb_groupnorm_plan)."""
+    import ctypes as C
+    from faceposegenerator_amd import _lib as L
+    o = [C.c_int32(-1) for _ in range(7)]
+    L.check(eng.lib.idb_groupnorm_plan(c0, c1, b, hw, groups, sync_len, 0, *[C.byref(x) for x in o]))
+    form, sw, _, chunks, chunk_len, pr, _ = [x.value for x in o]
+    return form, sw, chunks, chunk_len, pr
+
+
 @pytest.mark.parametrize("b,hw,c0,c1,silu,eps", [(2, 256, 64, 0, True, 1e-5), (3, 64, 320, 0, False, 1e-6), (2, 100, 1280, 640, True, 1e-5),
                                                  (1, 4096, 128, 0, True, 1e-6), (2, 64, 1280, 1280, True, 1e-5), (4, 1024, 640, 320, True, 1e-5),
                                                  (2, 1024, 1280, 640, True, 1e-5), (2, 1024, 640, 0, False, 1e-5), (2, 256, 1280, 0, True, 1e-5),
                                                  (3, 16, 64, 0, True, 1e-5), (2, 4, 128, 128, False, 1e-6), (2, 1600, 320, 0, True, 1e-5)])
 def test_groupnorm(eng, b, hw, c0, c1, silu, eps):
+    # the geometry each shape was picked for (idb_groupnorm_plan: slice channels, pixel chunks, chunk length): 64-, 80- and 120-channel slices
+    # (the last straddle x0 | x1), 1 .. 64 chunks, chunk lengths that are and are not multiples of the rows per pass, a short last chunk
+    assert _gn_plan(eng, c0, c1, b, hw)[:4] == (0,) + {(2, 256, 64, 0): (64, 4, 64), (3, 64, 320, 0): (80, 2, 32), (2, 100, 1280, 640): (120, 3, 34),
+                                                      (1, 4096, 128, 0): (64, 64, 64), (2, 64, 1280, 1280): (80, 2, 32), (4, 1024, 640, 320): (120, 31, 34),
+                                                      (2, 1024, 1280, 640): (120, 31, 34), (2, 1024, 640, 0): (80, 21, 49), (2, 256, 1280, 0): (80, 6, 43),
+                                                      (3, 16, 64, 0): (64, 1, 16), (2, 4, 128, 128): (64, 1, 4), (2, 1600, 320, 0): (80, 32, 50)}[b, hw, c0, c1]
     x0 = (_rand((b, hw, c0), 30) * 2 + 0.5).to(eng.tdt)
     x1 = (_rand((b, hw, c1), 31) - 1.0).to(eng.tdt) if c1 else None
     c = c0 + c1
@@ -303,6 +319,8 @@ def test_groupnorm_statistics_from_the_gemm(eng, b, side, cin, cout, split_k, re
     part = y._gn[0].view(b, hw // 64, 32, 2).double()
     assert torch.allclose(part[..., 0], yr.sum(dim=(2, 4)), rtol=1e-5, atol=1e-3)
     assert torch.allclose(part[..., 1], (yr * yr).sum(dim=(2, 4)), rtol=1e-5, atol=1e-3)
+    want, bnd = _gn_sums(y, b, hw, cout)         # and per partial: at most one fp32 addition per addend of the chunk, whatever the order
+    assert ((part - want).abs() <= bnd / 2).all(), ((part - want).abs() / bnd).max().item()
     y_plain = eng.gemm([(x, cin, 9, side, side, 0)], wp, cout, b, side, side, bias=bias, residual=resid, split_k=split_k)
     fused = eng.groupnorm(y, cout, None, 0, b, hw, gamma, beta, 1e-5, True, groups=32)
     assert y._gn is None
@@ -324,6 +342,8 @@ def test_groupnorm_single_launch_handoff(eng, b, hw, c0, c1):
     gamma, beta = _rand((c,), 32) * 0.2 + 1, _rand((c,), 33) * 0.1
     sync = torch.zeros(4096, dtype=torch.int32, device=DEV)
     st = torch.cuda.current_stream().cuda_stream
+    assert _gn_plan(eng, c0, c1, b, hw, sync.numel())[0] == 1, "this shape no longer takes the single-launch form"
+    assert _gn_plan(eng, c0, c1, b, hw)[0] == 0
 
     def gn(x0, x1, counters):
         out = torch.empty((b * hw, c), dtype=eng.tdt, device=DEV)
