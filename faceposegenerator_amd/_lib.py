@@ -150,3 +150,33 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load().idb_last_error()
         raise IdbError(f"{what or 'idb call'} failed (status {rc}): {msg.decode() if msg else ''}")
+
+
+# descriptor fields gemm_desc takes by name (everything but the positional ones)
+_DESC_FIELDS = frozenset(name for name, _ in GemmDesc._fields_) - {"dtype", "batch", "out_h", "out_w", "n", "nsrc", "src", "w"}
+
+
+def gemm_desc(dtype: int, srcs, w_ptr, n: int, batch: int, oh: int, ow: int, **fields) -> GemmDesc:
+    """The one place the package fills an idb_gemm_desc.  srcs: [(ptr, channels, taps, in_h, in_w[, upsample])]; every other
+    field of the descriptor by name (stride defaults to 1, out_dtype to dtype, out_ld to n; pointers as addresses or None)."""
+    unknown = set(fields) - _DESC_FIELDS
+    if unknown:
+        raise TypeError(f"gemm_desc: unknown idb_gemm_desc field(s) {sorted(unknown)}")
+    if len(srcs) > IDB_MAX_SRC:
+        raise ValueError(f"gemm_desc: {len(srcs)} sources, idb_gemm takes at most {IDB_MAX_SRC}")
+    d = GemmDesc()
+    d.dtype, d.batch, d.out_h, d.out_w, d.stride, d.n, d.nsrc = dtype, batch, oh, ow, 1, n, len(srcs)
+    for s, (ptr, ch, taps, ih, iw, *up) in zip(d.src, srcs):
+        s.ptr, s.channels, s.taps, s.in_h, s.in_w, s.upsample = ptr, ch, taps, ih, iw, (up[0] if up else 0)
+    d.w, d.out_dtype, d.out_ld = w_ptr, dtype, n
+    for k, v in fields.items():
+        setattr(d, k, v)
+    return d
+
+
+def run_gemm(lib, d: GemmDesc, workspace_fn, stream) -> int:
+    """idb_gemm on `d`: workspace_fn(nbytes) -> a device uint8 tensor of at least nbytes, asked only when the plan needs one.
+    Returns idb_gemm's status unchecked (the engine handles IDB_EUNSUPPORTED of a grouped launch itself)."""
+    need = lib.idb_gemm_workspace_bytes(C.byref(d))
+    ws = workspace_fn(need).data_ptr() if need > 0 else None
+    return lib.idb_gemm(C.byref(d), ws, need, stream)

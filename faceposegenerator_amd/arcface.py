@@ -17,13 +17,14 @@ Engine (every layer a HIP kernel of libidb_kernels.so):
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import OrderedDict
-from typing import Dict, List, Optional, Tuple
+from functools import partial
+from typing import Dict, List, Tuple
 
 import numpy as np
 import torch
 
+from . import _hipnet as N
 from . import _lib as L
 
 SD = Dict[str, torch.Tensor]
@@ -111,27 +112,11 @@ def synth_weights(arch: str = "r100", seed: int = 0) -> SD:
 
 def check_state_dict(sd: SD, arch: str) -> None:
     """Strict keys and shapes: missing / unexpected keys raise ValueError naming them; num_batches_tracked is accepted and ignored."""
-    shapes = param_shapes(arch)
-    need = {k for k in shapes if not k.endswith("num_batches_tracked")}
-    have = {k for k in sd if not k.endswith("num_batches_tracked")}
-    missing, extra = sorted(need - have), sorted(have - set(shapes))
-    if missing or extra:
-        raise ValueError(f"ArcFace {arch} state dict: missing keys {missing[:8]}{'...' if len(missing) > 8 else ''}, "
-                         f"unexpected keys {extra[:8]}{'...' if len(extra) > 8 else ''}")
-    for k in need:
-        if tuple(sd[k].shape) != shapes[k]:
-            raise ValueError(f"ArcFace {arch} state dict: {k} has shape {tuple(sd[k].shape)}, expected {shapes[k]}")
+    N.check_state_dict(sd, param_shapes(arch), f"ArcFace {arch}")
 
 
-def _affine(sd: SD, key: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    """eval-mode BatchNorm as y = a x + b (float64)."""
-    a = sd[f"{key}.weight"].double() / torch.sqrt(sd[f"{key}.running_var"].double() + EPS)
-    return a, sd[f"{key}.bias"].double() - sd[f"{key}.running_mean"].double() * a
-
-
-def _pack(w: torch.Tensor) -> torch.Tensor:
-    """[cout][cin][kh][kw] -> [cout][kh*kw*cin] ([tap][channel] K order of idb_gemm)."""
-    return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+_affine = partial(N.bn_affine, eps=EPS)          # eval-mode BatchNorm as y = a x + b (float64)
+_pack = N.pack_conv
 
 
 def fold_weights(sd: SD, arch: str = "r100") -> Dict[str, torch.Tensor]:
@@ -177,25 +162,22 @@ def fold_weights(sd: SD, arch: str = "r100") -> Dict[str, torch.Tensor]:
     return {k: v.float().contiguous() for k, v in f.items()}
 
 
-class ArcFace:
+class ArcFace(N.HipNet):
     """Drop-in for the reference's ``arcface_model(img)``: float [B,3,112,112] (already (x/255 - 0.5)/0.5) -> [B,512] fp32.
 
     ``ArcFace.from_pretrained(path)`` loads a local ``.pth`` (e.g. ArcFace_r100_ms1mv3_backbone.pth); ``.to("cuda:N")`` uploads the
     folded weights; ``embed_u8(crops)`` takes uint8 NHWC [B,112,112,3] crops (face_align.norm_crop output) with the preprocessing on
     the GPU.  Batches of any size >= 1 run in chunks of ``chunk`` faces."""
 
+    NAME = "ArcFace"
+    DTYPES = "float16 (the reference's autocast dtype) or bfloat16"
+
     def __init__(self, sd: SD, arch: str = "r100", torch_dtype: torch.dtype = torch.float16, chunk: int = 256):
-        if torch_dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError("ArcFace runs in float16 (the reference's autocast dtype) or bfloat16")
+        super().__init__(torch_dtype, chunk)
         check_state_dict(sd, arch)
-        self.arch, self.tdt = arch, torch_dtype
-        self.dt = L.IDB_F16 if torch_dtype == torch.float16 else L.IDB_BF16
+        self.arch = arch
         self._sd = {k: v.detach().cpu() for k, v in sd.items()}
         self._fw = fold_weights(self._sd, arch)
-        self.chunk = int(chunk)
-        self.device: Optional[torch.device] = None
-        self.lib = None
-        self._ws = None
 
     @classmethod
     def from_state_dict(cls, sd: SD, arch: str = "r100", torch_dtype: torch.dtype = torch.float16) -> "ArcFace":
@@ -211,56 +193,22 @@ class ArcFace:
         return cls(synth_weights(arch, seed), arch, torch_dtype)
 
     # ---- device side ----------------------------------------------------------------------------------------------------------
-    def to(self, device) -> "ArcFace":
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("ArcFace runs on the GPU only (HIP kernels); use .to('cuda:N')")
-        self.lib = L.load()
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        L.check(self.lib.idb_device_check(idx), "idb_device_check")
-        self.device = torch.device("cuda", idx)
-        self.w: Dict[str, torch.Tensor] = {}
-        for k, v in self._fw.items():
-            conv = k.endswith("conv1.w") or k.endswith("conv2.w")
-            self.w[k] = v.to(self.device, dtype=self.tdt if conv else torch.float32).contiguous()
-        self._blocks = [(i, j) for i, nb in enumerate(ARCHS[self.arch]) for j in range(nb)]
-        return self
-
-    def _need_device(self):
-        if self.device is None:
-            raise RuntimeError("call .to('cuda:N') first")
-
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _workspace(self, nbytes: int) -> Optional[torch.Tensor]:
-        if nbytes == 0:
-            return None
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
+    def _operand(self, key: str) -> bool:
+        return key.endswith("conv1.w") or key.endswith("conv2.w")
 
     def gemm(self, srcs, w, n, batch, oh, ow, bias, stride=1, slope=None, residual=None, out2=None, split_k=0, tile=0):
         """One idb_gemm: srcs = [(tensor NHWC, channels, taps, in_h, in_w)].  Returns (out, out2 or None)."""
         out = torch.empty((batch, oh, ow, n), dtype=self.tdt, device=self.device)
-        d = L.GemmDesc()
-        d.dtype, d.batch, d.out_h, d.out_w, d.stride, d.n, d.nsrc = self.dt, batch, oh, ow, stride, n, len(srcs)
-        for i, (t, ch, taps, ih, iw) in enumerate(srcs):
-            d.src[i].ptr, d.src[i].channels, d.src[i].taps, d.src[i].in_h, d.src[i].in_w = t.data_ptr(), ch, taps, ih, iw
-        d.w, d.bias = w.data_ptr(), bias.data_ptr()
-        d.out, d.out_dtype, d.out_ld = out.data_ptr(), self.dt, n
-        d.split_k, d.tile = split_k, tile
+        f = dict(bias=bias.data_ptr(), out=out.data_ptr(), stride=stride, split_k=split_k, tile=tile)
         if slope is not None:
-            d.act, d.act_slope = 2, slope.data_ptr()
+            f.update(act=2, act_slope=slope.data_ptr())
         if residual is not None:
-            d.residual = residual.data_ptr()
+            f["residual"] = residual.data_ptr()
         o2 = None
         if out2 is not None:
             o2 = torch.empty_like(out)
-            d.out2, d.out2_scale, d.out2_shift = o2.data_ptr(), out2[0].data_ptr(), out2[1].data_ptr()
-        need = self.lib.idb_gemm_workspace_bytes(C.byref(d))
-        ws = self._workspace(need)
-        L.check(self.lib.idb_gemm(C.byref(d), None if ws is None else ws.data_ptr(), need, self._stream()), "idb_gemm")
+            f.update(out2=o2.data_ptr(), out2_scale=out2[0].data_ptr(), out2_shift=out2[1].data_ptr())
+        self._gemm([(t.data_ptr(), *rest) for t, *rest in srcs], w.data_ptr(), n, batch, oh, ow, **f)
         return out, o2
 
     def stem(self, x: torch.Tensor, u8: bool) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -309,11 +257,7 @@ class ArcFace:
         return self.head(x)
 
     def _run(self, x: torch.Tensor, u8: bool) -> torch.Tensor:
-        self._need_device()
-        outs = []
-        for s in range(0, x.shape[0], self.chunk):
-            outs.append(self._forward(x[s:s + self.chunk].contiguous(), u8))
-        return outs[0] if len(outs) == 1 else torch.cat(outs)
+        return self._chunked(x, lambda xc: (self._forward(xc, u8),))[0]
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         """float [B,3,112,112] normalised as (x/255 - 0.5)/0.5 -> [B,512] fp32."""

@@ -2073,14 +2073,21 @@ extern "C" int32_t idb_gemm_fuses_groupnorm(const idb_gemm_desc* d) {
     return plan_gemm(d, &pl) == IDB_OK && gemm_fuses_gn(d, pl) ? 1 : 0;
 }
 
+// grouped weights (w_groups > 1) select the matrix per row tile: a tile must lie inside one group, and the persistent variant walks
+// tiles across groups.  When this holds idb_gemm refuses the grouped descriptor and the caller runs one launch per group on row
+// slices, which carry neither row statistics out nor a folded LayerNorm in
+static bool grouped_runs_per_group(const idb_gemm_desc* d, const Plan& pl) {
+    return d->w_groups > 1 && (pl.v->fam == kPersistent || d->w_group_rows % pl.v->bm != 0);
+}
+
 extern "C" int32_t idb_gemm_folds_layernorm(const idb_gemm_desc* d) {
     Plan pl;
-    return plan_gemm(d, &pl) == IDB_OK && gemm_folds_ln(d, pl) ? 1 : 0;
+    return plan_gemm(d, &pl) == IDB_OK && !grouped_runs_per_group(d, pl) && gemm_folds_ln(d, pl) ? 1 : 0;
 }
 
 extern "C" int32_t idb_gemm_row_stats_tiles(const idb_gemm_desc* d) {
     Plan pl;
-    if (plan_gemm(d, &pl) != IDB_OK || !gemm_uses_lds_epilogue(d, pl)) return 0;
+    if (plan_gemm(d, &pl) != IDB_OK || grouped_runs_per_group(d, pl) || !gemm_uses_lds_epilogue(d, pl)) return 0;
     return pl.tiles_n;
 }
 
@@ -2202,7 +2209,7 @@ extern "C" int idb_gemm(const idb_gemm_desc* d, void* workspace, size_t workspac
     if (p.w_groups > 1) {
         IDB_REQUIRE(d->w_group_rows > 0 && d->w_group_stride >= (long long)p.w_bytes && d->w_group_stride % 16 == 0 &&
                         (long long)d->w_groups * d->w_group_stride < (1LL << 40), "idb_gemm: w_groups needs w_group_rows > 0 and a 16-byte-multiple w_group_stride >= one matrix");
-        if (pl.v->fam == kPersistent || d->w_group_rows % pl.v->bm != 0) {
+        if (grouped_runs_per_group(d, pl)) {
             idb_set_error("idb_gemm: w_group_rows = %d is not a multiple of the plan's tile height %d (or the persistent variant was chosen): run one launch per group",
                           d->w_group_rows, pl.v->bm);
             return IDB_EUNSUPPORTED;

@@ -526,39 +526,24 @@ class HipEngine:
         own_out = out is None
         if out is None:
             out = self.arena.alloc((m, ncols), torch.float32 if out_f32 else self.tdt)
-        d = L.GemmDesc()
-        d.dtype, d.batch, d.out_h, d.out_w, d.stride, d.n, d.nsrc = self.dt, batch, oh, ow, stride, n, len(srcs)
-        for i, (t, ch, taps, ih, iw, up) in enumerate(srcs):
-            d.src[i].ptr, d.src[i].channels, d.src[i].taps = t.data_ptr(), ch, taps
-            d.src[i].in_h, d.src[i].in_w, d.src[i].upsample = ih, iw, up
-        d.w, d.bias = w.data_ptr(), _ptr(bias)
+        f = dict(stride=stride, bias=_ptr(bias), residual=_ptr(residual), geglu=int(geglu), out=out.data_ptr(),
+                 out_dtype=L.IDB_F32 if out_f32 else self.dt, out_ld=out.shape[-1], split_k=split_k, tile=tile, out_scale=out_scale, flags=flags,
+                 act=act, pad_mode=pad_mode, w_layout=1 if getattr(w, "_tiled", None) is not None else 0,
+                 counters=self._counters.data_ptr(), counters_len=self._counters.numel())
         if sbias is not None:
-            d.sample_bias = sbias[0].data_ptr() + 4 * sbias[1]
-            d.sample_bias_ld = sbias[2]
-        d.residual, d.geglu = _ptr(residual), int(geglu)
-        d.out, d.out_dtype, d.out_ld = out.data_ptr(), (L.IDB_F32 if out_f32 else self.dt), out.shape[-1]
-        d.split_k, d.tile, d.out_scale, d.flags, d.act = split_k, tile, out_scale, flags, act
-        d.pad_mode = pad_mode
+            f.update(sample_bias=sbias[0].data_ptr() + 4 * sbias[1], sample_bias_ld=sbias[2])
         if gn_in is not None:       # (partials, chunks, groups, eps, gamma, beta, silu, nsrc): GroupNorm(+SiLU) of the first nsrc sources in-kernel
-            d.gn_in_partials, d.gn_in_chunks, d.gn_in_groups, d.gn_in_eps = gn_in[0].data_ptr(), gn_in[1], gn_in[2], gn_in[3]
-            d.gn_in_gamma, d.gn_in_beta, d.gn_in_silu, d.gn_in_nsrc = gn_in[4].data_ptr(), gn_in[5].data_ptr(), int(gn_in[6]), gn_in[7]
-        d.w_layout = 1 if getattr(w, "_tiled", None) is not None else 0
+            f.update(gn_in_partials=gn_in[0].data_ptr(), gn_in_chunks=gn_in[1], gn_in_groups=gn_in[2], gn_in_eps=gn_in[3],
+                     gn_in_gamma=gn_in[4].data_ptr(), gn_in_beta=gn_in[5].data_ptr(), gn_in_silu=int(gn_in[6]), gn_in_nsrc=gn_in[7])
         G = getattr(w, "_groups", 0) or 0
         if G > 1:                                      # grouped weights: rows [r*M/rep + g*rpg, ... + rpg) of every CFG half r use matrix g
             rep = self._rep
             if m % (rep * G):
                 raise ValueError(f"grouped weights: {m} rows do not divide into {rep} x {G} groups")
-            d.w_groups, d.w_group_rows, d.w_group_stride = G, m // (rep * G), w.shape[1] * 2
-            tile_id = C.c_int32()
-            L.check(self.lib.idb_gemm_plan(C.byref(d), C.byref(tile_id), None, None), "idb_gemm_plan")
-            bm = {1: 128, 2: 128, 3: 64, 4: 64, 5: 128, 6: 64, 7: 64, 8: 128, 9: 128}[tile_id.value % 10] * (2 if tile_id.value // 10 >= 8 else 1)
-            if tile_id.value // 10 == 4 or d.w_group_rows % bm:
-                # this launch will run group by group on row slices (_gemm_per_group): no row statistics out, no folded LayerNorm in
-                row_stats = False
-                if ln is not None:
-                    if own_out:
-                        self.arena.free(out)
-                    return None
+            # where the library will refuse this launch (run group by group below), its two queries answer 0: no row statistics out,
+            # no folded LayerNorm in
+            f.update(w_groups=G, w_group_rows=m // (rep * G), w_group_stride=w.shape[1] * 2)
+        d = L.gemm_desc(self.dt, [(t.data_ptr(), *rest) for t, *rest in srcs], w.data_ptr(), n, batch, oh, ow, **f)
         rs_buf = None
         if row_stats and self._ln_fold:
             nt = self.lib.idb_gemm_row_stats_tiles(C.byref(d))
@@ -584,21 +569,19 @@ class HipEngine:
             if mode > 0 or gn_stats_always:      # gn_stats_always: tests of the library's extra-statistics-launch path
                 gn_part = self.arena.alloc((batch * (oh * ow // 64) * gn_stats * 2,), torch.float32)
                 d.gn_partials, d.gn_groups = gn_part.data_ptr(), gn_stats
-        d.counters, d.counters_len = self._counters.data_ptr(), self._counters.numel()
-        need = self.lib.idb_gemm_workspace_bytes(C.byref(d))
-        ws = self._workspace(need) if need else None
         log = self.launch_log
         if log is not None:                      # bench.py's per-kernel roofline accounting (eager pass only)
             tile, sk, blocks = C.c_int32(), C.c_int32(), C.c_int32()
             L.check(self.lib.idb_gemm_plan(C.byref(d), C.byref(tile), C.byref(sk), C.byref(blocks)), "idb_gemm_plan")
+            need = self.lib.idb_gemm_workspace_bytes(C.byref(d))
             k_total = sum(ch * taps for (_, ch, taps, _, _, _) in srcs)
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        rc = self.lib.idb_gemm(C.byref(d), _ptr(ws), need, _stream())
+        rc = L.run_gemm(self.lib, d, self._workspace, _stream())
         if rc == -2 and G > 1:
             # the plan's tile height does not divide the group's rows (cross-attention K/V of 77 tokens, tiny grids): one launch per
             # (CFG half, group) on row slices — the same arithmetic
-            self._gemm_per_group(d, G, m // (self._rep * G), w, ws, need, ln)
+            self._gemm_per_group(d, G, m // (self._rep * G))
         else:
             L.check(rc, "idb_gemm")
         if gn_part is not None:
@@ -608,31 +591,24 @@ class HipEngine:
         if log is not None:
             ev1.record()
             log.append({"tile": tile.value + (1000 if gn_in is not None else 0), "split_k": sk.value, "blocks": blocks.value, "m": m, "n": n, "k": k_total,
-                        "flops": 2.0 * m * n * k_total, "ev": (ev0, ev1), "desc": d, "ws": (ws, need),
+                        "flops": 2.0 * m * n * k_total, "ev": (ev0, ev1), "desc": d, "ws": (self._ws if need else None, need),
                         "bytes": 2.0 * (m * k_total / (9 if srcs[0][2] == 9 else 1) + n * k_total + m * ncols)})
         return out
 
-    def _gemm_per_group(self, d, G: int, rpg: int, w: torch.Tensor, ws, need: int, ln) -> None:
+    def _gemm_per_group(self, d, G: int, rpg: int) -> None:
         """Fallback of the grouped-weights GEMM for plain [M][K] sources: row slice [j*rpg, (j+1)*rpg) with matrix j % G."""
-        if d.nsrc != 1 or d.src[0].taps != 1 or d.src[0].in_h != 1 or d.gn_partials or d.row_stats_out:
-            raise L.IdbError("grouped weights: per-group fallback needs one plain [M][K] source without statistics outputs")
+        if d.nsrc != 1 or d.src[0].taps != 1 or d.src[0].in_h != 1 or d.gn_partials or d.row_stats_out or d.ln_stats:
+            raise L.IdbError("grouped weights: per-group fallback needs one plain [M][K] source without statistics outputs or a folded LayerNorm")
         m, k, esz = d.batch, d.src[0].channels, 2
         osz = 4 if d.out_dtype == L.IDB_F32 else 2
-        base = {"a": d.src[0].ptr, "out": d.out, "res": d.residual, "w": d.w, "u": d.ln_u, "v": d.ln_v, "st": d.ln_stats}
+        a0, out0, res0, w0 = d.src[0].ptr, d.out, d.residual, d.w
+        d.batch, d.w_groups = rpg, 0
         for j in range(m // rpg):
-            g = j % G
-            d.batch = rpg
-            d.src[0].ptr = base["a"] + j * rpg * k * esz
-            d.out = base["out"] + j * rpg * d.out_ld * osz
-            d.residual = None if not base["res"] else base["res"] + j * rpg * d.out_ld * esz
-            d.w = base["w"] + g * d.w_group_stride
-            if ln is not None:
-                d.ln_u, d.ln_v = base["u"] + g * d.n * 4, base["v"] + g * d.n * 4
-                d.ln_stats = base["st"] + j * rpg * d.ln_tiles * 8
-            d.w_groups = 0
-            need_j = self.lib.idb_gemm_workspace_bytes(C.byref(d))
-            wsj = self._workspace(need_j) if need_j else None
-            L.check(self.lib.idb_gemm(C.byref(d), _ptr(wsj), need_j, _stream()), "idb_gemm (per group)")
+            d.src[0].ptr = a0 + j * rpg * k * esz
+            d.out = out0 + j * rpg * d.out_ld * osz
+            d.residual = None if not res0 else res0 + j * rpg * d.out_ld * esz
+            d.w = w0 + (j % G) * d.w_group_stride
+            L.check(L.run_gemm(self.lib, d, self._workspace, _stream()), "idb_gemm (per group)")
 
     def fuses_groupnorm(self, src_shapes, w: torch.Tensor, n: int, batch: int, oh: int, ow: int, groups: int, nsrc_norm: int) -> bool:
         """Would idb_gemm apply the GroupNorm of the first `nsrc_norm` sources inside the kernel for this shape?  src_shapes:
@@ -642,15 +618,10 @@ class HipEngine:
         key = (tuple(src_shapes), n, batch, oh, ow, groups, nsrc_norm, getattr(w, "_tiled", None) is not None)
         hit = self._gn_conv_cache.get(key)
         if hit is None:
-            d = L.GemmDesc()
             dummy = self._gn_ws.data_ptr()
-            d.dtype, d.batch, d.out_h, d.out_w, d.stride, d.n, d.nsrc = self.dt, batch, oh, ow, 1, n, len(src_shapes)
-            for i, (ch, taps) in enumerate(src_shapes):
-                d.src[i].ptr, d.src[i].channels, d.src[i].taps, d.src[i].in_h, d.src[i].in_w = dummy, ch, taps, oh, ow
-            d.w, d.out, d.out_dtype, d.out_ld = dummy, dummy, self.dt, n
-            d.w_layout = 1 if getattr(w, "_tiled", None) is not None else 0
-            d.gn_in_partials, d.gn_in_chunks, d.gn_in_groups, d.gn_in_eps, d.gn_in_nsrc = dummy, 1, groups, 1e-5, nsrc_norm
-            d.gn_in_gamma = d.gn_in_beta = dummy
+            d = L.gemm_desc(self.dt, [(dummy, ch, taps, oh, ow) for ch, taps in src_shapes], dummy, n, batch, oh, ow, out=dummy,
+                            w_layout=1 if getattr(w, "_tiled", None) is not None else 0, gn_in_partials=dummy, gn_in_chunks=1,
+                            gn_in_groups=groups, gn_in_eps=1e-5, gn_in_nsrc=nsrc_norm, gn_in_gamma=dummy, gn_in_beta=dummy)
             hit = self._gn_conv_cache[key] = self.lib.idb_gemm_fuses_groupnorm(C.byref(d)) > 0
         return hit
 
@@ -803,11 +774,8 @@ class HipEngine:
         key = (rows, c, n, geglu)
         hit = self._fold_cache.get(key)
         if hit is None:
-            d = L.GemmDesc()
-            d.dtype, d.batch, d.out_h, d.out_w, d.stride, d.n, d.nsrc = self.dt, rows, 1, 1, 1, n, 1
-            d.src[0].ptr, d.src[0].channels, d.src[0].taps, d.src[0].in_h, d.src[0].in_w = x.data_ptr(), c, 1, 1, 1
-            d.w, d.geglu = x.data_ptr(), int(geglu)
-            d.out, d.out_dtype, d.out_ld = x.data_ptr(), self.dt, (n // 2 if geglu else n)
+            d = L.gemm_desc(self.dt, [(x.data_ptr(), c, 1, 1, 1)], x.data_ptr(), n, rows, 1, 1, geglu=int(geglu), out=x.data_ptr(),
+                            out_ld=n // 2 if geglu else n)
             hit = self._fold_cache[key] = self.lib.idb_gemm_folds_layernorm(C.byref(d)) > 0
         return hit
 

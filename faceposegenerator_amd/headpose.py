@@ -26,13 +26,13 @@ Engine (every layer a HIP kernel of libidb_kernels.so):
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
+from . import _hipnet as N
 from . import _lib as L
 
 SD = Dict[str, torch.Tensor]
@@ -138,22 +138,12 @@ def check_state_dict(sd: SD) -> None:
     raise ValueError naming them; num_batches_tracked is accepted and ignored."""
     sd = _normalize_keys(sd)
     deploy = is_deploy(sd)
-    shapes = param_shapes(deploy)
-    need = {k for k in shapes if not k.endswith("num_batches_tracked")}
-    have = {k for k in sd if not k.endswith("num_batches_tracked")}
-    missing, extra = sorted(need - have), sorted(have - set(shapes))
-    form = "deploy" if deploy else "training"
-    if missing or extra:
-        raise ValueError(f"6DRepNet ({form} form) state dict: missing keys {missing[:8]}{'...' if len(missing) > 8 else ''}, "
-                         f"unexpected keys {extra[:8]}{'...' if len(extra) > 8 else ''}")
-    for k in sorted(need):
-        if tuple(sd[k].shape) != shapes[k]:
-            raise ValueError(f"6DRepNet ({form} form) state dict: {k} has shape {tuple(sd[k].shape)}, expected {shapes[k]}")
+    N.check_state_dict(sd, param_shapes(deploy), f"6DRepNet ({'deploy' if deploy else 'training'} form)")
 
 
 def _fuse_bn(w: torch.Tensor, sd: SD, key: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    t = sd[f"{key}.weight"].double() / torch.sqrt(sd[f"{key}.running_var"].double() + EPS)
-    return w * t[:, None, None, None], sd[f"{key}.bias"].double() - sd[f"{key}.running_mean"].double() * t
+    t, b = N.bn_affine(sd, key, EPS)
+    return w * t[:, None, None, None], b
 
 
 def reparam_block(sd: SD, key: str, cin: int, cout: int, groups: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -186,10 +176,7 @@ def deploy_state_dict(sd: SD) -> SD:
     return out
 
 
-def _pack(w: torch.Tensor) -> torch.Tensor:
-    """[cout][cin/g][kh][kw] -> [cout][kh*kw*cin/g] ([tap][channel] K order of idb_gemm; for a grouped conv, row block g is group g's
-    matrix)."""
-    return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+_pack = N.pack_conv
 
 
 def fold_weights(sd: SD) -> Dict[str, torch.Tensor]:
@@ -221,22 +208,17 @@ def pose_summary(names: Sequence[str], pitch, yaw, roll) -> dict:
     return res
 
 
-class HeadPose:
+class HeadPose(N.HipNet):
     """Drop-in for SixDRepNet: ``model(x)`` maps normalised fp32 [B,3,224,224] to rotation matrices [B,3,3] (``SixDRepNet.forward``);
     ``predict_u8(images, pad=30)`` maps uint8 RGB [B,S,S,3] images to (pitch, yaw, roll) fp32 degree tensors [B] — the notebook's
     ``model.predict`` on the image with its 30-pixel border.  ``HeadPose.from_pretrained(path)`` loads a local ``.pth`` (deploy or
     training form); nothing is ever downloaded.  Batches of any size >= 1 run in chunks of ``chunk`` images."""
 
+    NAME = "HeadPose"
+
     def __init__(self, sd: SD, torch_dtype: torch.dtype = torch.float16, chunk: int = 256):
-        if torch_dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError("HeadPose runs in float16 or bfloat16")
-        self.tdt = torch_dtype
-        self.dt = L.IDB_F16 if torch_dtype == torch.float16 else L.IDB_BF16
+        super().__init__(torch_dtype, chunk)
         self._fw = fold_weights({k: v.detach().cpu() for k, v in _normalize_keys(sd).items()})
-        self.chunk = int(chunk)
-        self.device: Optional[torch.device] = None
-        self.lib = None
-        self._ws = None
 
     @classmethod
     def from_state_dict(cls, sd: SD, torch_dtype: torch.dtype = torch.float16) -> "HeadPose":
@@ -251,46 +233,15 @@ class HeadPose:
         return cls(synth_weights(seed, deploy), torch_dtype)
 
     # ---- device side ----------------------------------------------------------------------------------------------------------
-    def to(self, device) -> "HeadPose":
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("HeadPose runs on the GPU only (HIP kernels); use .to('cuda:N')")
-        self.lib = L.load()
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        L.check(self.lib.idb_device_check(idx), "idb_device_check")
-        self.device = torch.device("cuda", idx)
-        self.w: Dict[str, torch.Tensor] = {}
-        for k, v in self._fw.items():
-            gemm = k.endswith(".w") and k.startswith("layer") and k != "layer0.w"
-            self.w[k] = v.to(self.device, dtype=self.tdt if gemm else torch.float32).contiguous()
-        return self
-
-    def _need_device(self):
-        if self.device is None:
-            raise RuntimeError("call .to('cuda:N') first")
-
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _workspace(self, nbytes: int) -> Optional[torch.Tensor]:
-        if nbytes == 0:
-            return None
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
+    def _operand(self, key: str) -> bool:
+        return key.endswith(".w") and key.startswith("layer") and key != "layer0.w"
 
     def gemm(self, src: int, cin: int, h: int, w_: int, batch: int, weight: int, bias: int, n: int, out: int, out_ld: int, stride: int = 1,
              act: int = 3, split_k: int = 0, tile: int = 0) -> None:
         """One 3x3 pad-1 idb_gemm on raw device pointers: src NHWC [batch][h][w_][cin] -> out rows of out_ld elements."""
-        d = L.GemmDesc()
         oh, ow = (h + stride - 1) // stride, (w_ + stride - 1) // stride
-        d.dtype, d.batch, d.out_h, d.out_w, d.stride, d.n, d.nsrc = self.dt, batch, oh, ow, stride, n, 1
-        d.src[0].ptr, d.src[0].channels, d.src[0].taps, d.src[0].in_h, d.src[0].in_w = src, cin, 9, h, w_
-        d.w, d.bias, d.out, d.out_dtype, d.out_ld = weight, bias, out, self.dt, out_ld
-        d.act, d.split_k, d.tile = act, split_k, tile
-        need = self.lib.idb_gemm_workspace_bytes(C.byref(d))
-        ws = self._workspace(need)
-        L.check(self.lib.idb_gemm(C.byref(d), None if ws is None else ws.data_ptr(), need, self._stream()), "idb_gemm")
+        self._gemm([(src, cin, 9, h, w_)], weight, n, batch, oh, ow, stride=stride, bias=bias, out=out, out_ld=out_ld, act=act,
+                   split_k=split_k, tile=tile)
 
     def block(self, i: int, x, split_out: bool):
         """Block i (1..27) of blocks().  x: a full NHWC tensor [B,H,W,cin] (dense block) or [G,B,H,W,cin/G] (grouped block).
@@ -362,15 +313,7 @@ class HeadPose:
         return x
 
     def _run(self, x: torch.Tensor, u8: bool, pad: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
-        Rs, As = [], []
-        for s in range(0, x.shape[0], self.chunk):
-            xc = x[s:s + self.chunk].contiguous()
-            if u8:
-                xc = self.resize(xc, pad)
-            R, a = self.head(self.features(xc, u8))
-            Rs.append(R)
-            As.append(a)
-        return (Rs[0], As[0]) if len(Rs) == 1 else (torch.cat(Rs), torch.cat(As))
+        return self._chunked(x, lambda xc: self.head(self.features(self.resize(xc, pad) if u8 else xc, u8)))
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         """float [B,3,224,224] normalised with the ImageNet mean / std -> rotation matrices [B,3,3] fp32."""

@@ -165,13 +165,16 @@ size_t idb_gemm_workspace_bytes(const idb_gemm_desc* d);
  * on 256-row tiles, 10: patch-resident 3x3 conv on the shape's own 64-/128-row tile), split-K factor and workgroup count.
  * Host-only, no GPU call. */
 int idb_gemm_plan(const idb_gemm_desc* d, int32_t* tile, int32_t* split_k, int32_t* blocks);
-/* Column tiles of the plan idb_gemm would run for `d` if that plan can emit row statistics (LDS-staged epilogue), else 0. */
+/* Column tiles of the plan idb_gemm would run for `d` if that plan can emit row statistics (LDS-staged epilogue), else 0.  Also 0 for
+ * a grouped descriptor (w_groups > 1) that idb_gemm refuses (w_group_rows no multiple of the plan's tile height, or the persistent
+ * variant): the caller's one-launch-per-group run emits no row statistics. */
 int32_t idb_gemm_row_stats_tiles(const idb_gemm_desc* d);
 /* Would idb_gemm produce gn_partials for `groups` groups WITHOUT an extra statistics launch?  0: no (it would launch one — the caller's
  * two-pass idb_groupnorm is as good); 1: from its split-K reduce launch; 2: from its own LDS-staged epilogue (no split-K, 160-wide
  * tiles holding whole groups). */
 int32_t idb_gemm_emits_gn_partials(const idb_gemm_desc* d, int32_t groups);
-/* 1 if the plan idb_gemm would run for `d` (bias / sample_bias NULL, one 1x1 source) can apply a folded LayerNorm (ln_*). */
+/* 1 if the plan idb_gemm would run for `d` (bias / sample_bias NULL, one 1x1 source) can apply a folded LayerNorm (ln_*); 0 as well
+ * for a grouped descriptor (w_groups > 1) that idb_gemm refuses, as idb_gemm_row_stats_tiles. */
 int32_t idb_gemm_folds_layernorm(const idb_gemm_desc* d);
 /* 1 if idb_gemm would run `d` with its fused GroupNorm (gn_in_* set) in ONE launch. */
 int32_t idb_gemm_fuses_groupnorm(const idb_gemm_desc* d);

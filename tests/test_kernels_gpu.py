@@ -1028,3 +1028,42 @@ def test_fused_groupnorm_proj_in_no_silu_with_row_stats(eng):
         xr = ref.double().reshape(b * h * h, nt, -1)
         rs = ref._rs[0].double().reshape(b * h * h, nt, 2)
         assert torch.allclose(rs[..., 0], xr.sum(-1), rtol=1e-5, atol=1e-3) and torch.allclose(rs[..., 1], (xr * xr).sum(-1), rtol=1e-5, atol=1e-3)
+
+
+@pytest.mark.parametrize("rpg,launches", [(64, 1), (77, 4)])
+def test_grouped_weights_gemm_in_one_launch_and_per_group(eng, rpg, launches):
+    """eng.gemm with grouped weights (G = 2, CFG repeat 2: row slice j uses matrix j % 2) on both sides of its fallback: 64 rows per
+    group are whole 64-row tiles (one grouped launch, row statistics out), 77 are not (one launch per slice, no row statistics).
+    Every slice must equal the ungrouped launch on its rows with its matrix bit for bit; ``_rs`` follows idb_gemm_row_stats_tiles
+    of the grouped descriptor."""
+    import ctypes as C
+    from faceposegenerator_amd import _lib as L
+    n = k = 320
+    G, rep = 2, 2
+    m = rep * G * rpg
+    a = _rand((m, k), 131).to(eng.tdt)
+    bias = _rand((n,), 132)
+    mats = [eng.tile_weight(_rand((n, k), 133 + g, k ** -0.5).to(eng.tdt)) for g in range(G)]
+    wg = torch.stack([t.reshape(-1) for t in mats])
+    wg._groups, wg._tiled = G, (n, k)
+    prev, eng._rep = eng._rep, rep
+    try:
+        before = eng.lib.idb_launch_count()
+        out = eng.gemm([(a, k, 1, 1, 1, 0)], wg, n, m, 1, 1, bias=bias, row_stats=True)
+        assert eng.lib.idb_launch_count() - before == launches
+    finally:
+        eng._rep = prev
+    for j in range(rep * G):
+        rows = slice(j * rpg, (j + 1) * rpg)
+        ref = eng.gemm([(a[rows], k, 1, 1, 1, 0)], mats[j % G], n, rpg, 1, 1, bias=bias)
+        assert torch.equal(out[rows], ref), j
+    d = L.GemmDesc()
+    d.dtype, d.batch, d.out_h, d.out_w, d.stride, d.n, d.nsrc = eng.dt, m, 1, 1, 1, n, 1
+    d.src[0].ptr, d.src[0].channels, d.src[0].taps, d.src[0].in_h, d.src[0].in_w = a.data_ptr(), k, 1, 1, 1
+    d.w, d.bias, d.out, d.out_dtype, d.out_ld, d.w_layout = wg.data_ptr(), bias.data_ptr(), out.data_ptr(), eng.dt, n, 1
+    d.w_groups, d.w_group_rows, d.w_group_stride = G, rpg, wg.shape[1] * 2
+    tiles = eng.lib.idb_gemm_row_stats_tiles(C.byref(d))
+    assert (tiles > 0) == (launches == 1)
+    assert (getattr(out, "_rs", None) is not None) == (eng._ln_fold and tiles > 0)
+    if getattr(out, "_rs", None) is not None:
+        assert out._rs[1] == tiles

@@ -5,9 +5,8 @@
   python tools/bench_lw.py [B_eff]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import ctypes as C
 import torch
-from faceposegenerator_amd import spec as S, _lib as L
+from faceposegenerator_amd import spec as S
 from faceposegenerator_amd.engine import HipEngine
 beff = int(sys.argv[1]) if len(sys.argv) > 1 else 2
 eng = HipEngine(S.TINY_UNET, S.TINY_VAE, None, None, "cuda:0", "f16")
@@ -26,7 +25,6 @@ for (h, cin, cout, taps) in shapes:
     srcs = [(x, cin, 9, h, h, 0)] if taps == 9 else [(x, cin, 1, 1, 1, 0)]
     dims = (beff, h, h) if taps == 9 else (m, 1, 1)
     # the plan the library picks (tile, split-K), then the same tile shape / split as loader-wave variants
-    d = L.GemmDesc()
     eng.launch_log = []
     eng.gemm(srcs, ws[0], cout, *dims, bias=bias, out=out)
     e = eng.launch_log[0]; eng.launch_log = None
