@@ -30,6 +30,7 @@ EXPORTS = [
     "idb_quantize_fp8", "idb_pack_weight_fp8", "idb_gemm_fp8", "idb_groupnorm_fp8",
     "idb_arcface_stem", "idb_arcface_head_workspace_bytes", "idb_arcface_head",
     "idb_resize_aa_u8", "idb_pose_stem", "idb_pose_head",
+    "idb_resize_bicubic_aa_u8", "idb_vit_patchify", "idb_vit_tokens", "idb_vit_head",
 ]
 
 
@@ -137,6 +138,10 @@ def load() -> C.CDLL:
         "idb_resize_aa_u8": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
         "idb_pose_stem": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
         "idb_pose_head": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
+        "idb_resize_bicubic_aa_u8": (C.c_int, [vp, i32, i32, i32, vp, vp]),
+        "idb_vit_patchify": (C.c_int, [vp, i32, i32, vp, i32, vp]),
+        "idb_vit_tokens": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        "idb_vit_head": (C.c_int, [vp, i64, i32, i32, vp, vp, f32, vp, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

@@ -1,7 +1,8 @@
 // 6DRepNet head pose (sixdrepnet SixDRepNet_Detector: RepVGG-B1g2 in deploy form + a 6D rotation head; ID-Booth's
 // Evaluation/PoseEstimation notebook): the pieces that are not implicit GEMMs.  The 27 3x3 blocks after the stem run on idb_gemm
 // (act = 3, ReLU); faceposegenerator_amd/headpose.py drives them.
-//   resize: Pillow's antialiased BILINEAR resize (torchvision Resize on a PIL image) of the zero-padded uint8 image, bit-exact
+//   resize: Pillow's antialiased BILINEAR resize (torchvision Resize on a PIL image) of the zero-padded uint8 image, bit-exact;
+//           the same passes with the BICUBIC filter serve DINOv2's transform (idb_resize_bicubic_aa_u8)
 //   stem:   /255, ImageNet normalisation, conv 3->64 3x3 stride 2 pad 1 + bias + ReLU — 3 input channels: VALU work
 //   head:   global average pool, linear 2048->6, Gram-Schmidt to a rotation matrix, Euler angles in degrees, all fp32
 #include "idb_common.h"
@@ -17,12 +18,25 @@ namespace {
 // its uint8 result feeds the vertical pass.  Both axes have the same coefficients (square images).  The double arithmetic must not
 // be contracted into FMAs: Pillow's x86 build rounds every product and sum.
 constexpr int RS_KMAX = 16, RS_DMAX = 256, RS_PREC = 22;
+// The filters of Resample.c: BILINEAR (support 1) and BICUBIC (Keys cubic with a = -0.5, support 2), in Pillow's operation order.
+enum { RS_BILINEAR = 0, RS_BICUBIC = 1 };
 
+template <int FILTER>
+__device__ __forceinline__ double resize_filter(double t) {
+#pragma clang fp contract(off)
+    if (t < 0.0) t = -t;
+    if constexpr (FILTER == RS_BILINEAR) return t < 1.0 ? 1.0 - t : 0.0;
+    if (t < 1.0) return (1.5 * t - 2.5) * t * t + 1;
+    if (t < 2.0) return (((t - 5) * t + 8) * t - 4) * -0.5;
+    return 0.0;
+}
+
+template <int FILTER>
 __device__ int resize_coeffs(int o, int in, int out, int* k) {
 #pragma clang fp contract(off)
     const double scale = (double)in / out;
     const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = fs, ss = 1.0 / fs;
+    const double support = (FILTER == RS_BICUBIC ? 2.0 : 1.0) * fs, ss = 1.0 / fs;
     const double center = (o + 0.5) * scale;
     int xmin = (int)(center - support + 0.5);
     if (xmin < 0) xmin = 0;
@@ -31,9 +45,7 @@ __device__ int resize_coeffs(int o, int in, int out, int* k) {
     xmax -= xmin;
     double w[RS_KMAX], ww = 0.0;
     for (int x = 0; x < xmax; ++x) {
-        double t = (x + xmin - center + 0.5) * ss;
-        if (t < 0.0) t = -t;
-        w[x] = t < 1.0 ? 1.0 - t : 0.0;
+        w[x] = resize_filter<FILTER>((x + xmin - center + 0.5) * ss);
         ww += w[x];
     }
     for (int x = 0; x < RS_KMAX; ++x) {
@@ -51,7 +63,8 @@ __device__ __forceinline__ unsigned char clip8(int ss) {
 // One workgroup per (output row, image).  Coefficients for all D output columns (= rows) into LDS; the horizontal pass then produces
 // only the <= RS_KMAX padded input rows this output row reads, and the vertical pass combines them.  An input row is thus resampled
 // horizontally by every output row whose window covers it (about 2-3 rows at 572 -> 224): cheaper than a workspace round trip.
-// Sums stay below 2^31: 255 * sum k_i < 255 * 2^22 * (1 + taps * 2^-22).
+// Sums stay below 2^31: 255 * sum |k_i| < 255 * 2^22 * 1.5 (the bicubic lobes add up to less than 1.5 in absolute value).
+template <int FILTER>
 __global__ __launch_bounds__(256) void resize_aa_kernel(const unsigned char* __restrict__ src, int S, int pad, int D,
                                                         unsigned char* __restrict__ dst) {
     __shared__ int kc[RS_DMAX][RS_KMAX];
@@ -59,7 +72,7 @@ __global__ __launch_bounds__(256) void resize_aa_kernel(const unsigned char* __r
     __shared__ unsigned char rows[RS_KMAX][RS_DMAX * 3];
     const int oy = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int P = S + 2 * pad;
-    for (int o = tid; o < D; o += 256) kb[o] = resize_coeffs(o, P, D, kc[o]);
+    for (int o = tid; o < D; o += 256) kb[o] = resize_coeffs<FILTER>(o, P, D, kc[o]);
     __syncthreads();
     const int y0 = kb[oy] & 0xffff, ny = kb[oy] >> 16;
     const unsigned char* img = src + (long long)b * S * S * 3;
@@ -213,17 +226,28 @@ __global__ __launch_bounds__(256) void pose_head_kernel(const T* __restrict__ x,
 
 }  // namespace
 
-extern "C" int idb_resize_aa_u8(const void* src, int32_t batch, int32_t s, int32_t pad, int32_t d, void* dst, void* stream) {
-    IDB_REQUIRE(src && dst, "idb_resize_aa_u8: null pointer");
+// filter: the taps one output sample reads are at most ceil(support) * 2 + 1 (Resample.c's ksize), support = (1 or 2) max(P / d, 1)
+template <int FILTER>
+static int resize_launch(const char* api, const void* src, int32_t batch, int32_t s, int32_t pad, int32_t d, void* dst, void* stream) {
+    IDB_REQUIRE(src && dst, "%s: null pointer", api);
     IDB_REQUIRE(batch > 0 && batch <= 65535 && s > 0 && pad >= 0 && d > 0 && d <= RS_DMAX && (long long)s * s * 3 * batch < (1LL << 40),
-                "idb_resize_aa_u8: batch 1..65535, s > 0, pad >= 0, d 1..%d", RS_DMAX);
+                "%s: batch 1..65535, s > 0, pad >= 0, d 1..%d", api, RS_DMAX);
     const long long P = (long long)s + 2LL * pad;
     const double fs = (double)P / d < 1.0 ? 1.0 : (double)P / d;
-    IDB_REQUIRE(P < 65536 && (int)ceil(fs) * 2 + 1 <= RS_KMAX, "idb_resize_aa_u8: reduction %lld -> %d needs more than %d taps", P, d, RS_KMAX);
-    hipLaunchKernelGGL(resize_aa_kernel, dim3(d, batch), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)src, s, pad, d,
+    const double support = (FILTER == RS_BICUBIC ? 2.0 : 1.0) * fs;
+    IDB_REQUIRE(P < 65536 && (int)ceil(support) * 2 + 1 <= RS_KMAX, "%s: reduction %lld -> %d needs more than %d taps", api, P, d, RS_KMAX);
+    hipLaunchKernelGGL((resize_aa_kernel<FILTER>), dim3(d, batch), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)src, s, pad, d,
                        (unsigned char*)dst);
-    IDB_CHECK_LAUNCH("idb_resize_aa_u8");
+    IDB_CHECK_LAUNCH(api);
     return IDB_OK;
+}
+
+extern "C" int idb_resize_aa_u8(const void* src, int32_t batch, int32_t s, int32_t pad, int32_t d, void* dst, void* stream) {
+    return resize_launch<RS_BILINEAR>("idb_resize_aa_u8", src, batch, s, pad, d, dst, stream);
+}
+
+extern "C" int idb_resize_bicubic_aa_u8(const void* src, int32_t batch, int32_t s, int32_t d, void* dst, void* stream) {
+    return resize_launch<RS_BICUBIC>("idb_resize_bicubic_aa_u8", src, batch, s, 0, d, dst, stream);
 }
 
 extern "C" int idb_pose_stem(const void* x, int32_t x_u8, int32_t batch, int32_t h, int32_t w, const float* weight, const float* bias,

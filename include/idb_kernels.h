@@ -426,6 +426,29 @@ int idb_pose_stem(const void* x, int32_t x_u8, int32_t batch, int32_t h, int32_t
 int idb_pose_head(const void* x, int32_t batch, int32_t hw, int32_t c, const float* weight, const float* bias, float* rot, float* angles,
                   int32_t dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * DINOv2 ViT image encoder (facebookresearch/dinov2 DinoVisionTransformer, ViT-S/B/L with 14x14 patches; the `--model dinov2` encoder of
+ * ID-Booth's dgm-eval run) — the layers that are not idb_layernorm / idb_gemm / idb_attention calls.
+ *   idb_resize_bicubic_aa_u8: replaces torchvision Resize((d, d), BICUBIC) on a PIL image = Image.resize((d, d), BICUBIC): uint8 HWC RGB
+ *       [batch][s][s][3] -> [batch][d][d][3] with Pillow's antialiased Keys cubic (a = -0.5, support 2 max(s / d, 1)), 22-bit fixed-point
+ *       coefficients, horizontal pass clipped to 8 bits, then the vertical pass; bit-exact with Pillow.  d <= 256, at most 16 taps per
+ *       axis (ceil(2 s / d) <= 7: 768 -> 224 needs 15); a larger reduction is IDB_EINVAL before any launch.
+ *   idb_vit_patchify: replaces the unfold of PatchEmbed.proj (Conv2d(3, D, 14, stride 14)): 224x224 input -> [batch * 256][640] operand
+ *       dtype, one row per patch in row-major patch order, column (c * 14 + ky) * 14 + kx (the conv weight's own flattening), columns
+ *       588..639 zero.  x: uint8 NHWC [batch][224][224][3] when x_u8 (ToTensor + ImageNet Normalize fused, fp32), else normalised fp32
+ *       NCHW [batch][3][224][224].
+ *   idb_vit_tokens: replaces prepare_tokens_with_masks (no masks): out[b][0] = cls + pos[0], out[b][1 + t] = patches[b n_patches + t] +
+ *       pos[1 + t]; cls [dim] and pos [1 + n_patches][dim] fp32, patches / out operand dtype, fp32 add, one rounding.  dim % 8 == 0.
+ *   idb_vit_head: replaces the final nn.LayerNorm for x_norm_clstoken (head = Identity): LayerNorm of row b * row_stride of x [..][dim]
+ *       (operand dtype) for b < batch, in fp32 (two passes, fixed summation order: deterministic) -> fp32 [batch][dim].
+ * ------------------------------------------------------------------------------------------ */
+int idb_resize_bicubic_aa_u8(const void* src, int32_t batch, int32_t s, int32_t d, void* dst, void* stream);
+int idb_vit_patchify(const void* x, int32_t x_u8, int32_t batch, void* out, int32_t dtype, void* stream);
+int idb_vit_tokens(const void* patches, const float* cls, const float* pos, void* out, int32_t batch, int32_t n_patches, int32_t dim,
+                   int32_t dtype, void* stream);
+int idb_vit_head(const void* x, int64_t row_stride, int32_t batch, int32_t dim, const float* gamma, const float* beta, float eps, float* out,
+                 int32_t dtype, void* stream);
+
 int idb_vae_sample(const float* moments, const float* noise, float scale, float* latents, float* mean_out,
                    float* logvar_out, int32_t batch, int32_t channels, int32_t hw, void* stream);
 
