@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("IDB_LIB") or os.path.join(_HERE, "libidb_kernels.so")
 
 IDB_BF16, IDB_F16, IDB_F32 = 0, 1, 2
 IDB_MAX_SRC = 4
+IDB_PAIR_DIST2, IDB_PAIR_KNN, IDB_PAIR_PRDC, IDB_PAIR_NEAREST, IDB_PAIR_POLY = 0, 1, 2, 3, 4
 
 # every symbol include/idb_kernels.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -31,6 +32,7 @@ EXPORTS = [
     "idb_arcface_stem", "idb_arcface_head_workspace_bytes", "idb_arcface_head",
     "idb_resize_aa_u8", "idb_pose_stem", "idb_pose_head",
     "idb_resize_bicubic_aa_u8", "idb_vit_patchify", "idb_vit_tokens", "idb_vit_head",
+    "idb_pair_workspace_bytes", "idb_pair_dist2", "idb_pair_knn_radii", "idb_pair_prdc_counts", "idb_pair_nearest", "idb_pair_poly_sums",
 ]
 
 
@@ -142,6 +144,12 @@ def load() -> C.CDLL:
         "idb_vit_patchify": (C.c_int, [vp, i32, i32, vp, i32, vp]),
         "idb_vit_tokens": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
         "idb_vit_head": (C.c_int, [vp, i64, i32, i32, vp, vp, f32, vp, i32, vp]),
+        "idb_pair_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "idb_pair_dist2": (C.c_int, [vp, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+        "idb_pair_knn_radii": (C.c_int, [vp, i32, i32, vp, i32, vp, vp, sz, vp]),
+        "idb_pair_prdc_counts": (C.c_int, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "idb_pair_nearest": (C.c_int, [vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
+        "idb_pair_poly_sums": (C.c_int, [vp, i32, vp, i32, i32, vp, vp, i32, i32, f32, f32, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

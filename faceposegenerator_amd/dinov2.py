@@ -2,7 +2,8 @@
 ``python -m dgm_eval ... --model dinov2 --metrics prdc vendi fd kd authpct``).  dgm-eval loads ``dinov2_vitl14`` from the hub, feeds
 every image through ``Resize((224, 224), BICUBIC)`` on the PIL image, ``ToTensor`` and the ImageNet ``Normalize`` (its ``transform``
 with ``clean_resize=False``) and stores ``model(x)`` — the final LayerNorm's class token, ``head = Identity`` — as one float32
-``[N, D]`` matrix; all five metrics are CPU code over that matrix and stay the reference's.
+``[N, D]`` matrix; all five metrics are CPU code over that matrix in the reference.  Here ``metrics.py`` computes them from that
+matrix: PRDC, KD and AuthPct on the GPU (``idb_pair_*``), FD and per-class Vendi as float64 host code.
 
 Neither ``dinov2`` nor ``dgm_eval`` is part of this project.  The state-dict layout, the position-embedding interpolation and the
 block order below restate facebookresearch/dinov2's published ``vision_transformer.py`` (ViT-S/B/L with 14x14 patches, LayerScale,

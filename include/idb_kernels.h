@@ -449,6 +449,49 @@ int idb_vit_tokens(const void* patches, const float* cls, const float* pos, void
 int idb_vit_head(const void* x, int64_t row_stride, int32_t batch, int32_t dim, const float* gamma, const float* beta, float eps, float* out,
                  int32_t dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * All-pairs metrics over fp32 image features [N][D] (dgm-eval's PRDC, KD and AuthPct as ID-Booth's evaluation runs them on DINOv2
+ * features), on the exact f32-input MFMA.  d2(i, j) = max(|a_i - s|^2 + |b_j - s|^2 - 2 (a_i - s).(b_j - s), 0) with the caller's
+ * shift s [D] (NULL: none) subtracted where the operands are loaded; any d >= 1 (K is zero-padded in the kernel), rows dense with
+ * stride d.  Only idb_pair_dist2 writes the N x N matrix.  Every entry takes a workspace of idb_pair_workspace_bytes(mode, ...) bytes,
+ * 16-byte aligned, writes all of its outputs, uses integer atomics and fixed-order float sums only (bit-identical from run to run)
+ * and validates its arguments before any HIP call.  n <= 2^22, d <= 2^16.
+ *   idb_pair_workspace_bytes(mode, na, nb, subsets): mode IDB_PAIR_*; KNN takes n as na; POLY takes the subset size m as na and the
+ *       number of subsets; 0 for arguments the entry would refuse.
+ *   idb_pair_dist2: replaces sklearn.metrics.pairwise_distances(a, b) ** 2 / torch.cdist(a, b) ** 2: out [na][nb].  The test hook
+ *       that pins the engine's numerics, and the form for tiny inputs.
+ *   idb_pair_knn_radii: replaces prdc.py's compute_nearest_neighbour_distances (get_kth_value(pairwise_distances(x, x), k =
+ *       nearest_k + 1)), squared: r2[i] = the kth smallest of row i of d2(x, x) with the diagonal forced to exactly 0 (the point
+ *       itself is the first), equal distances counted with their multiplicity.  1 <= kth <= min(8, n).
+ *   idb_pair_prdc_counts: replaces the three N x N comparisons of prdc.py's compute_prdc in one pass over d2(real, gen), given the
+ *       squared radii of both sets: in_real_sphere[j] = #{i : d2(i, j) < r2_real[i]} (precision = mean(> 0), density = sum / (k ng)),
+ *       covered[i] = any_j d2(i, j) < r2_gen[j] as 0 / 1 (recall), row_min[i] = min_j d2(i, j) (coverage = mean(row_min < r2_real)).
+ *   idb_pair_nearest: replaces torch.cdist(a, b).min(dim = 0) of authpct.py: min_d2[j] = min_i d2(i, j) and argmin[j] = that i, the
+ *       lowest on an exact tie; exclude_diag leaves i == j out (a set against itself; needs na >= 2).
+ *   idb_pair_poly_sums: replaces the three polynomial_kernel matrices of mmd.py's polynomial_mmd, per subset: rows idx_x[s][m] of x
+ *       [nx][d] and idx_y[s][m] of y [ny][d] (int32 device arrays, every index in range: not checked) are gathered where the operands
+ *       are loaded, k(a, b) = (gamma a.b + coef0)^3 on the unshifted features; sums[s][0] = sum_{i != j} k(x_i, x_j), sums[s][1] =
+ *       sum_{i != j} k(y_i, y_j), sums[s][2] = sum_{i, j} k(x_i, y_j), double: fp32 per 128 x 128 tile, the tiles added in row-major
+ *       order in double on the device.  One launch covers the 3 * subsets matrices; subsets <= 21845, 2 <= m <= min(nx, ny).
+ * ------------------------------------------------------------------------------------------ */
+#define IDB_PAIR_DIST2 0
+#define IDB_PAIR_KNN 1
+#define IDB_PAIR_PRDC 2
+#define IDB_PAIR_NEAREST 3
+#define IDB_PAIR_POLY 4
+size_t idb_pair_workspace_bytes(int32_t mode, int32_t na, int32_t nb, int32_t subsets);
+int idb_pair_dist2(const float* a, int32_t na, const float* b, int32_t nb, int32_t d, const float* shift, float* out, void* ws,
+                   size_t ws_bytes, void* stream);
+int idb_pair_knn_radii(const float* x, int32_t n, int32_t d, const float* shift, int32_t kth, float* r2, void* ws, size_t ws_bytes,
+                       void* stream);
+int idb_pair_prdc_counts(const float* real, int32_t nr, const float* gen, int32_t ng, int32_t d, const float* shift, const float* r2_real,
+                         const float* r2_gen, int32_t* in_real_sphere, int32_t* covered, float* row_min, void* ws, size_t ws_bytes,
+                         void* stream);
+int idb_pair_nearest(const float* a, int32_t na, const float* b, int32_t nb, int32_t d, const float* shift, int32_t exclude_diag,
+                     float* min_d2, int32_t* argmin, void* ws, size_t ws_bytes, void* stream);
+int idb_pair_poly_sums(const float* x, int32_t nx, const float* y, int32_t ny, int32_t d, const int32_t* idx_x, const int32_t* idx_y,
+                       int32_t subsets, int32_t m, float gamma, float coef0, double* sums, void* ws, size_t ws_bytes, void* stream);
+
 int idb_vae_sample(const float* moments, const float* noise, float scale, float* latents, float* mean_out,
                    float* logvar_out, int32_t batch, int32_t channels, int32_t hw, void* stream);
 
