@@ -139,6 +139,8 @@ extern "C" int idb_crop_resize_area_u8(const uint8_t* src, int32_t batch, int32_
                                        int32_t n, float* out, int32_t out_h, int32_t out_w, float sub, float mul, void* stream) {
     IDB_REQUIRE(src && boxes && out && batch > 0 && h > 0 && w > 0 && channels > 0 && n >= 0 && out_h > 0 && out_w > 0,
                 "idb_crop_resize_area_u8: bad arguments");
+    // the kernel's window count (ye - ys) * (xe - xs) is an int product over a box that lies inside one image; boxes[k * 5] an int index
+    IDB_REQUIRE((long long)h * w < (1LL << 31) && n <= (1 << 28), "idb_crop_resize_area_u8: image plane or box count too large");
     if (n == 0) return IDB_OK;
     const long long total = (long long)n * channels * out_h * out_w;
     IDB_REQUIRE(total < (1LL << 31) * 256, "idb_crop_resize_area_u8: too many outputs");
@@ -151,6 +153,8 @@ extern "C" int idb_crop_resize_area_u8(const uint8_t* src, int32_t batch, int32_
 extern "C" int idb_conv2d_f32(const float* x, const float* w, const float* bias, const float* prelu, float* y, int32_t batch, int32_t cin,
                               int32_t h, int32_t w_, int32_t cout, int32_t kh, int32_t kw, void* stream) {
     IDB_REQUIRE(x && w && y && batch > 0 && cin > 0 && cout > 0 && kh > 0 && kw > 0 && h >= kh && w_ >= kw, "idb_conv2d_f32: bad arguments");
+    // the kernel indexes one input plane (ky * w + kx) and one filter ((ci * kh + ky) * kw + kx) with int
+    IDB_REQUIRE((long long)h * w_ < (1LL << 31) && (long long)cin * kh * kw < (1LL << 31), "idb_conv2d_f32: plane or filter too large");
     const long long total = (long long)batch * cout * (h - kh + 1) * (w_ - kw + 1);
     IDB_REQUIRE(total < (1LL << 31) * 256, "idb_conv2d_f32: too many outputs");
     hipLaunchKernelGGL(conv2d_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, w, bias, prelu, y, batch,
@@ -161,8 +165,12 @@ extern "C" int idb_conv2d_f32(const float* x, const float* w, const float* bias,
 
 extern "C" int idb_maxpool2d_f32(const float* x, float* y, int32_t planes, int32_t h, int32_t w, int32_t k, int32_t stride, void* stream) {
     IDB_REQUIRE(x && y && planes > 0 && h > 0 && w > 0 && k > 0 && stride > 0, "idb_maxpool2d_f32: bad arguments");
+    // int in the kernel: yy * w + xx inside one plane, oy * stride + ky < h + k + stride; int in pool_out: n + stride - k
+    IDB_REQUIRE((long long)h * w < (1LL << 31) && h <= (1 << 30) && w <= (1 << 30) && k <= (1 << 20) && stride <= (1 << 20),
+                "idb_maxpool2d_f32: plane, window or stride too large");
     const int oh = pool_out(h, k, stride), ow = pool_out(w, k, stride);
     const long long total = (long long)planes * oh * ow;
+    IDB_REQUIRE(total < (1LL << 31) * 256, "idb_maxpool2d_f32: too many outputs");
     hipLaunchKernelGGL(maxpool2d_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, planes, h, w, k,
                        stride, oh, ow);
     IDB_CHECK_LAUNCH("idb_maxpool2d_f32");
@@ -172,6 +180,7 @@ extern "C" int idb_maxpool2d_f32(const float* x, float* y, int32_t planes, int32
 extern "C" int idb_softmax_pairs_f32(const float* x, float* p1, int32_t batch, int32_t hw, void* stream) {
     IDB_REQUIRE(x && p1 && batch > 0 && hw > 0, "idb_softmax_pairs_f32: bad arguments");
     const long long total = (long long)batch * hw;
+    IDB_REQUIRE(total < (1LL << 31) * 256, "idb_softmax_pairs_f32: too many outputs");
     hipLaunchKernelGGL(softmax_pairs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, p1, batch, hw);
     IDB_CHECK_LAUNCH("idb_softmax_pairs_f32");
     return IDB_OK;

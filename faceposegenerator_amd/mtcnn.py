@@ -153,6 +153,13 @@ def pyramid_scales(h: int, w: int, min_face_size: int = 20, factor: float = 0.70
     return out
 
 
+def pool_out(n: int, k: int, s: int) -> int:
+    """Output size of nn.MaxPool2d(k, s, ceil_mode=True) along an axis of n: the last window must start inside the input (the rule of
+    pool_out in csrc/idb_mtcnn.hip; tests/test_detect_matrix_cpu.py compares it with torch over a grid)."""
+    v = (n - k + s - 1) // s + 1
+    return max(1, v - 1 if (v - 1) * s >= n else v)
+
+
 class MTCNN:
     def __init__(self, image_size: int = 160, margin: int = 0, min_face_size: int = 20, thresholds=(0.6, 0.7, 0.7), factor: float = 0.709,
                  post_process: bool = True, select_largest: bool = True, keep_all: bool = False, device="cuda:0",
@@ -184,11 +191,7 @@ class MTCNN:
 
     def _pool(self, x, k, s):
         b, c, h, w_ = x.shape
-
-        def o(n):
-            v = (n - k + s - 1) // s + 1
-            return max(1, v - 1 if (v - 1) * s >= n else v)
-        y = torch.empty((b, c, o(h), o(w_)), dtype=torch.float32, device=self.device)
+        y = torch.empty((b, c, pool_out(h, k, s), pool_out(w_, k, s)), dtype=torch.float32, device=self.device)
         L.check(self.lib.idb_maxpool2d_f32(x.data_ptr(), y.data_ptr(), b * c, h, w_, k, s, self._st()), "idb_maxpool2d_f32")
         return y
 

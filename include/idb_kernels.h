@@ -342,6 +342,9 @@ int idb_warp_affine_u8(const uint8_t* src, int32_t batch, int32_t h, int32_t w, 
  *       upstream's nms_numpy "Min" with +1 widths, use_min = 1 / plus_one = 1): boxes fp32 [n][4] SORTED by descending score, optional
  *       image index int32 [n] (boxes of different images never suppress each other); mask uint64 [n][(n+63)/64], bit j of row i set
  *       when box i would remove box j > i.  The greedy scan over the rows stays with the caller (host: a few hundred words).
+ *   Limits (IDB_EINVAL before any launch): one image or activation plane h * w < 2^31 elements and a filter cin * kh * kw < 2^31 (the
+ *       kernels index inside them with int); pooling h, w <= 2^30 and k, stride <= 2^20; at most 2^28 boxes and, for idb_nms_mask, 2^20;
+ *       fewer than 2^39 outputs per call; n = 0 boxes is IDB_OK without a launch.
  * ------------------------------------------------------------------------------------------ */
 int idb_crop_resize_area_u8(const uint8_t* src, int32_t batch, int32_t h, int32_t w, int32_t channels, const int32_t* boxes, int32_t n,
                             float* out, int32_t out_h, int32_t out_w, float sub, float mul, void* stream);
