@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("IDB_LIB") or os.path.join(_HERE, "libidb_kernels.so")
 IDB_BF16, IDB_F16, IDB_F32 = 0, 1, 2
 IDB_MAX_SRC = 4
 IDB_PAIR_DIST2, IDB_PAIR_KNN, IDB_PAIR_PRDC, IDB_PAIR_NEAREST, IDB_PAIR_POLY = 0, 1, 2, 3, 4
+# the selected points of idb_verif_roc, in the order of its points / ints outputs
+IDB_VERIF_POINTS = ("eer_t2", "eer_t1", "fmr0", "fmr1000", "fmr100", "fmr20", "fmr10", "fnmr0", "fnmr100", "fnmr1000", "youden", "mcc", "first")
 
 # every symbol include/idb_kernels.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -33,6 +35,7 @@ EXPORTS = [
     "idb_resize_aa_u8", "idb_pose_stem", "idb_pose_head",
     "idb_resize_bicubic_aa_u8", "idb_vit_patchify", "idb_vit_tokens", "idb_vit_head",
     "idb_pair_workspace_bytes", "idb_pair_dist2", "idb_pair_knn_radii", "idb_pair_prdc_counts", "idb_pair_nearest", "idb_pair_poly_sums",
+    "idb_verif_cos_scores", "idb_verif_workspace_bytes", "idb_verif_roc",
 ]
 
 
@@ -150,6 +153,9 @@ def load() -> C.CDLL:
         "idb_pair_prdc_counts": (C.c_int, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "idb_pair_nearest": (C.c_int, [vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
         "idb_pair_poly_sums": (C.c_int, [vp, i32, vp, i32, i32, vp, vp, i32, i32, f32, f32, vp, vp, sz, vp]),
+        "idb_verif_cos_scores": (C.c_int, [vp, i32, vp, i32, i32, vp, vp, i32, vp, vp]),
+        "idb_verif_workspace_bytes": (sz, [i32, i32]),
+        "idb_verif_roc": (C.c_int, [vp, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

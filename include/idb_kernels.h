@@ -495,6 +495,53 @@ int idb_pair_nearest(const float* a, int32_t na, const float* b, int32_t nb, int
 int idb_pair_poly_sums(const float* x, int32_t nx, const float* y, int32_t ny, int32_t d, const int32_t* idx_x, const int32_t* idx_y,
                        int32_t subsets, int32_t m, float gamma, float coef0, double* sums, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Identity-verification statistics (ID-Booth's Evaluation/PyEER_analysis: genuine / impostor cosine scores of ArcFace embeddings, then
+ * pyeer's get_eer_stats).  Everything is double.  Every entry validates its arguments before any HIP call, writes all of its outputs,
+ * uses fixed-order float sums and no float atomics (bit-identical from run to run) and never synchronises.
+ *   idb_verif_cos_scores: replaces utils.pairwise_cos_sim (1 - scipy.spatial.distance.cosine(e1, e2) per pair, a Python loop in 5-10
+ *       processes): out[p] = 1 - clip(1 - uv / sqrt(uu vv), 0, 2) for rows u = a[idx_a[p]], v = b[idx_b[p]] of the dense fp32 matrices
+ *       a [na][d], b [nb][d] (a == b allowed); uv, uu, vv summed in double from the fp32 operands (exact products), all three in one
+ *       order, so a row against itself is within 2^-52 of 1.  idx_a, idx_b: int32 [n_pairs] device arrays; an index out of range
+ *       reads nothing and gives NaN, as does a zero row (upstream's 0 / 0).  Any d >= 1 (16-byte loads when d % 4 == 0 and both
+ *       bases are 16-byte aligned), 1 <= n_pairs <= 2^30.
+ *   idb_verif_workspace_bytes(ng, ni): the workspace of idb_verif_roc; 0 for counts it would refuse.
+ *   idb_verif_roc: replaces pyeer's calculate_roc (a Python sort of (score, label) tuples, cumsum, unique) and the reductions of
+ *       get_eer_stats over it, from the ascending finite score arrays g_sorted [ng] and i_sorted [ni], 1 <= ng, ni <= 2^30.  The
+ *       thresholds are the distinct scores; at threshold t, fnm = #{genuine < t}, fm = #{impostor >= t}, fmr = fm / ni and fnmr =
+ *       fnm / ng as IEEE double quotients.  points [IDB_VERIF_POINTS] receives the threshold of every selected point below and ints
+ *       [2 p], ints [2 p + 1] its fm and fnm (NaN and -1, -1 when no threshold qualifies, which only the two EER points can):
+ *         IDB_VERIF_EER_T2 the smallest t with fmr - fnmr <= 0; IDB_VERIF_EER_T1 the largest t with fmr - fnmr > 0 (get_eer_values;
+ *           the caller chooses between them and handles the no-crossing case as upstream does);
+ *         IDB_VERIF_FMR0 / 1000 / 100 / 20 / 10 the first (smallest t) argmin of |fmr - op|, op = 0, 0.001, 0.01, 0.05, 0.1 (get_fmr_op);
+ *         IDB_VERIF_FNMR0 / 100 / 1000 the last (largest t) argmin of |fnmr - op|, op = 0, 0.01, 0.001 (get_fnmr_op);
+ *         IDB_VERIF_YOUDEN the first argmax of 1 - fnmr - fmr (get_youden_index); IDB_VERIF_MCC the first argmax of upstream's
+ *           Matthews expression, separate square roots and a zero denominator replaced by 1 (get_matthews_ccoef);
+ *         IDB_VERIF_FIRST the smallest threshold (upstream's index 0).
+ *       ints [2 IDB_VERIF_POINTS + 0] = the number of thresholds, [+ 1] = those with fmr - fnmr <= 0, [+ 2] = the exact integer
+ *       2 ni ng AUC = the sum over consecutive thresholds of (fm1 - fm2) (2 ng - fnm1 - fnm2) (calculate_roc_auc; <= 2^61).
+ *       moments [4] = gmean, gstd, imean, istd: np.mean and np.std (population, two passes).  ws 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+#define IDB_VERIF_POINTS 13
+#define IDB_VERIF_EER_T2 0
+#define IDB_VERIF_EER_T1 1
+#define IDB_VERIF_FMR0 2
+#define IDB_VERIF_FMR1000 3
+#define IDB_VERIF_FMR100 4
+#define IDB_VERIF_FMR20 5
+#define IDB_VERIF_FMR10 6
+#define IDB_VERIF_FNMR0 7
+#define IDB_VERIF_FNMR100 8
+#define IDB_VERIF_FNMR1000 9
+#define IDB_VERIF_YOUDEN 10
+#define IDB_VERIF_MCC 11
+#define IDB_VERIF_FIRST 12
+int idb_verif_cos_scores(const float* a, int32_t na, const float* b, int32_t nb, int32_t d, const int32_t* idx_a, const int32_t* idx_b,
+                         int32_t n_pairs, double* out, void* stream);
+size_t idb_verif_workspace_bytes(int32_t ng, int32_t ni);
+int idb_verif_roc(const double* g_sorted, int32_t ng, const double* i_sorted, int32_t ni, double* points, int64_t* ints, double* moments,
+                  void* ws, size_t ws_bytes, void* stream);
+
 int idb_vae_sample(const float* moments, const float* noise, float scale, float* latents, float* mean_out,
                    float* logvar_out, int32_t batch, int32_t channels, int32_t hw, void* stream);
 
