@@ -36,6 +36,7 @@ EXPORTS = [
     "idb_resize_bicubic_aa_u8", "idb_vit_patchify", "idb_vit_tokens", "idb_vit_head",
     "idb_pair_workspace_bytes", "idb_pair_dist2", "idb_pair_knn_radii", "idb_pair_prdc_counts", "idb_pair_nearest", "idb_pair_poly_sums",
     "idb_verif_cos_scores", "idb_verif_workspace_bytes", "idb_verif_roc",
+    "idb_frb_pair_dist", "idb_frb_workspace_bytes", "idb_frb_fold_counts",
 ]
 
 
@@ -156,6 +157,9 @@ def load() -> C.CDLL:
         "idb_verif_cos_scores": (C.c_int, [vp, i32, vp, i32, i32, vp, vp, i32, vp, vp]),
         "idb_verif_workspace_bytes": (sz, [i32, i32]),
         "idb_verif_roc": (C.c_int, [vp, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
+        "idb_frb_pair_dist": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),
+        "idb_frb_workspace_bytes": (sz, [i32, i32, i32]),
+        "idb_frb_fold_counts": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

@@ -542,6 +542,33 @@ size_t idb_verif_workspace_bytes(int32_t ng, int32_t ni);
 int idb_verif_roc(const double* g_sorted, int32_t ng, const double* i_sorted, int32_t ni, double* points, int64_t* ints, double* moments,
                   void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The LFW-style 10-fold pair benchmark of a face-recognition backbone (ID-Booth's FR_training/utils/verification.py, behind
+ * test_FR.py's accuracies on LFW, CFP-FP, AgeDB-30, CALFW, CPLFW).  Everything is double.  Every entry validates its arguments before
+ * any HIP call, uses fixed-order float sums and no float atomics (bit-identical from run to run) and never synchronises.
+ *   idb_frb_pair_dist: replaces embedding_preprocessing (embeddings_list[0] + embeddings_list[1], sklearn.preprocessing.normalize, the
+ *       per-row np.linalg.norm loop behind _xnorm) and calculate_roc's np.subtract / np.square / np.sum.  e0, e1: dense fp32
+ *       [2 n_pairs][d], the embeddings of the images and of their horizontal mirrors; rows 2p and 2p + 1 are pair p.  Per row
+ *       s = (double) e0 + (double) e1 (exact), n = sqrt(sum s_k^2), x = s / n, or x = s when n == 0 (sklearn's rule for a zero row);
+ *       dist[p] = sum_k (x[2p][k] - x[2p+1][k])^2.  norms: double [2][2 n_pairs], the Euclidean norms of the rows of e0, then of e1
+ *       (upstream's _xnorm is their mean).  Both rows of a pair take the same elements in the same order: identical inputs give
+ *       exactly 0.  1 <= n_pairs <= 2^30, 1 <= d <= 8192 (16-byte loads when d % 4 == 0 and both bases are 16-byte aligned).
+ *   idb_frb_workspace_bytes(n_pairs, nfolds, n_thr): the workspace of idb_frb_fold_counts; 0 for arguments it would refuse.
+ *   idb_frb_fold_counts: replaces the calculate_accuracy loops of calculate_roc (nfolds x 2 x n_thr numpy passes over the pairs).
+ *       dist: double [n_pairs]; issame: uint8 [n_pairs], non-zero = same identity; fold_start: int32 [nfolds + 1] device array, fold f
+ *       is the contiguous test block [fold_start[f], fold_start[f + 1]) of KFold(n_splits, shuffle=False) (a pair outside
+ *       [fold_start[0], fold_start[nfolds]) is counted nowhere); thresholds: double [n_thr], non-decreasing.  counts: int32
+ *       [nfolds][n_thr][2], [f][t][0] = #{p in fold f : issame[p] and dist[p] < thresholds[t]}, [f][t][1] the same for not issame[p];
+ *       the comparison is np.less, strict, double against double (a NaN distance is below nothing).  A histogram over
+ *       u = #{t : thresholds[t] <= dist[p]} per (fold, label) with integer atomics, then a prefix sum over t:
+ *       O(n_pairs log n_thr + nfolds n_thr).  1 <= n_pairs <= 2^30, 1 <= nfolds <= min(64, n_pairs), 1 <= n_thr <= 16384; ws 16-byte
+ *       aligned.
+ * ------------------------------------------------------------------------------------------ */
+int idb_frb_pair_dist(const float* e0, const float* e1, int32_t n_pairs, int32_t d, double* dist, double* norms, void* stream);
+size_t idb_frb_workspace_bytes(int32_t n_pairs, int32_t nfolds, int32_t n_thr);
+int idb_frb_fold_counts(const double* dist, const uint8_t* issame, int32_t n_pairs, const int32_t* fold_start, int32_t nfolds,
+                        const double* thresholds, int32_t n_thr, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
+
 int idb_vae_sample(const float* moments, const float* noise, float scale, float* latents, float* mean_out,
                    float* logvar_out, int32_t batch, int32_t channels, int32_t hw, void* stream);
 
