@@ -64,6 +64,15 @@ def knn_radii_scale(x, kth, mu):
     return np.maximum(d[np.arange(len(d)), nbr], 0.0), nrm + nrm[nbr]
 
 
+def knn_table(x, kmax):
+    """(radii [n][kmax], neighbours [n][kmax]): column kth - 1 holds what knn_radii_scale(x, kth, .) takes its radius and its scale
+    from, for every kth up to kmax from one sort."""
+    d = dist2(x, x)
+    np.fill_diagonal(d, -1.0)
+    nbr = np.argsort(d, axis=1, kind="stable")[:, :kmax]
+    return np.maximum(np.take_along_axis(d, nbr, axis=1), 0.0), nbr
+
+
 def undecided(gap, scl, tau=TAU):
     return gap <= tau * scl
 
