@@ -37,6 +37,7 @@ EXPORTS = [
     "idb_pair_workspace_bytes", "idb_pair_dist2", "idb_pair_knn_radii", "idb_pair_prdc_counts", "idb_pair_nearest", "idb_pair_poly_sums",
     "idb_verif_cos_scores", "idb_verif_workspace_bytes", "idb_verif_roc",
     "idb_frb_pair_dist", "idb_frb_workspace_bytes", "idb_frb_fold_counts",
+    "idb_resize_linear_u8", "idb_fiqa_tail",
 ]
 
 
@@ -160,6 +161,8 @@ def load() -> C.CDLL:
         "idb_frb_pair_dist": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),
         "idb_frb_workspace_bytes": (sz, [i32, i32, i32]),
         "idb_frb_fold_counts": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, vp, vp, sz, vp]),
+        "idb_resize_linear_u8": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+        "idb_fiqa_tail": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

@@ -569,6 +569,28 @@ size_t idb_frb_workspace_bytes(int32_t n_pairs, int32_t nfolds, int32_t n_thr);
 int idb_frb_fold_counts(const double* dist, const uint8_t* issame, int32_t n_pairs, const int32_t* fold_start, int32_t nfolds,
                         const double* thresholds, int32_t n_thr, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CR-FIQA face-image quality (ID-Booth's Evaluation/CR-FIQA/getQualityScore_FR_ID-Booth_12-2024.py: an IResNet with a `qs` linear
+ * head, run on the whole generated image squashed to 112x112) — the two pieces that are not ArcFace IResNet calls.  Both validate
+ * their arguments before any HIP call and never synchronise.
+ *   idb_resize_linear_u8: replaces `image = cv2.resize(image, (112, 112))` of get_batch_feature (:61; OpenCV INTER_LINEAR on 8-bit data) and,
+ *       with swap_rb, the BGR order `cv2.imread(image_path)` (:59) delivers: uint8 NHWC [batch][h][w][3] -> [batch][dh][dw][3], channels 0
+ *       and 2 exchanged on the way out when swap_rb.  h, w, dh, dw are independent (1..32768 each).  The caller supplies OpenCV's
+ *       per-axis tables, built on the host in OpenCV's float32 / float64 types (fiqa.coef_tables): ofs_* int32 [d] = the first source
+ *       index, coef_* int16 [d][2] = the two taps on an 11-bit scale (c0 + c1 = 2048); the second tap is min(ofs + 1, size - 1).  The
+ *       kernel is integer arithmetic only (int32 horizontal pass, then (((b0 (r0 >> 4)) >> 16) + ((b1 (r1 >> 4)) >> 16) + 2) >> 2),
+ *       and clamps the offsets to the image.  h == 2 dh and w == 2 dw takes OpenCV's 2x2 box (a + b + c + d + 2) >> 2 instead (the
+ *       tables are then unused but still required).  The tables must be 4-byte aligned.
+ *   idb_fiqa_tail: replaces `qs = self.qs(x)` of iresnet.py's forward (:178) and `features = normalize(features)` (:72; sklearn, l2) of
+ *       get_batch_feature, on emb fp32 [batch][d] (the output of idb_arcface_head): qs[b] = fp32(sum_i emb[b][i] weight[i] + bias[0]) and
+ *       emb_norm[b] = fp32(emb[b] / sqrt(sum_i emb[b][i]^2)), both sums in double in a fixed order (no atomics: bit-identical from run
+ *       to run), one rounding each; a zero row stays zero.  weight fp32 [d], bias fp32 [1], device memory.  1 <= d <= 8192.
+ * ------------------------------------------------------------------------------------------ */
+int idb_resize_linear_u8(const void* src, int32_t batch, int32_t h, int32_t w, const int32_t* ofs_x, const int16_t* coef_x,
+                         const int32_t* ofs_y, const int16_t* coef_y, int32_t dh, int32_t dw, int32_t swap_rb, void* dst, void* stream);
+int idb_fiqa_tail(const float* emb, const float* weight, const float* bias, int32_t batch, int32_t d, float* qs, float* emb_norm,
+                  void* stream);
+
 int idb_vae_sample(const float* moments, const float* noise, float scale, float* latents, float* mean_out,
                    float* logvar_out, int32_t batch, int32_t channels, int32_t hw, void* stream);
 
