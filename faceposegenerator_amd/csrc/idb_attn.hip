@@ -15,6 +15,12 @@
 //                 (no LDS round trip for P); V^T fragments come from the row-major V tile through
 //                 ds_read_b64_tr_b16 (hardware transpose read), in the k-order the accumulator imposes.
 // LDS rows are padded (K: 144 B, V: 192 B) so ds_read_b128 / ds_read_b64_tr_b16 are conflict-free.
+//
+// What bounds it (profiles/r04): the vector instructions a wave issues per tile, not the K/V round trip.  The Q-fragment waits
+// that once stood in the tile loop (every tile then waited for its own prefetch) cost 5 % of the 12-wave launch and 1.5 % of
+// the 4-wave one; with them gone, n = 4096 at B_eff 128 runs at 44.7 % MFMA busy (41.5 % before) and SQ_WAIT_ANY fell by 36 %.
+// The rest is the softmax: per 32 scores 16 v_exp_f32 (8 issue cycles each), 16 FMAs, 16 adds, 8 max3, 8 conversions.  Staging
+// addresses ride on a scalar tile base; the key-split forms issue the FMAs and the row sum as float pairs.
 #include "idb_common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -63,20 +69,48 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const T* __restrict__ q, 
     // staging: thread loads 16-B chunk (tid&7) of rows (tid>>3) + 8*NW*i of the K and V tiles into registers and writes them
     // to the other LDS buffer after the current tile's MFMAs.  PF register sets: PF = 1 fetches tile t+1 during tile t; PF = 2
     // would fetch tile t+2 (kept as a switch; see below).
-    constexpr int PF = 1;   // PF = 2 measured slower: 167 VGPRs (one workgroup per CU) or spills under a 128-VGPR cap, and a tile's
-                            // time is the S -> softmax -> PV dependency chain of a wave, not the K/V round trip
+    constexpr int PF = 1;   // PF = 2 re-measured with the Q-load waits out of the loop (so that the prefetch really overlaps): slower in every
+                            // form, 4096 keys 78.5-79.8 -> 85.8-88.0 us at B_eff 2 (12 waves, 163 VGPRs), 3358 -> 3816 us at B_eff 128
+                            // (4 waves: 206 VGPRs, two workgroups per CU instead of three).  One tile of look-ahead covers the round trip.
     constexpr int CH = NW >= 8 ? 1 : 8 / NW, RSTEP = NW >= 8 ? 64 : 8 * NW;     // NW > 8: waves 8.. do not stage
     const bool stager = NW <= 8 || tid < 512;                                    // wave-uniform
     const int srow = tid >> 3, schunk = tid & 7;
     V8 kreg[PF][CH], vreg[PF][CH];
+    // byte offset of the thread's chunk inside a tile, per staged row (32 bits: the host checks that 64 rows fit); the tile's base
+    // address is wave-uniform, so a full tile's loads need no per-tile vector address arithmetic.  Only the last, partial tile clamps
+    // its rows (masked later, must stay finite).
+    unsigned soff[CH];
+#pragma unroll
+    for (int i = 0; i < CH; ++i) soff[i] = (unsigned)((srow + RSTEP * i) * kv_ld + schunk * 8) * (unsigned)sizeof(T);
     auto gload = [&](auto SET, int t) {
         constexpr int st = decltype(SET)::value;
         if (!stager) return;
+        const long long tb = (long long)t * KV_TILE * kv_ld * (long long)sizeof(T);
+        // readfirstlane keeps the tile's base one scalar pointer (global_load ... v_off, s[base]): without it the compiler folds
+        // the offset into 64-bit vector adds per load
+        using GP = const __attribute__((address_space(1))) char*;
+        using GV8 = const __attribute__((address_space(1))) V8*;
+        auto scalar = [](const char* p_) {
+            const unsigned long long a = (unsigned long long)p_;
+            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+            return (GP)(((unsigned long long)hi << 32) | lo);
+        };
+        const GP kt_ = scalar((const char*)kbase + tb);
+        const GP vt_ = scalar((const char*)vbase + tb);
+        if ((t + 1) * KV_TILE <= n_kv) {
 #pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int row = min(t * KV_TILE + srow + RSTEP * i, n_kv - 1);   // clamp: masked later, must stay finite
-            kreg[st][i] = *(const V8*)(kbase + (long long)row * kv_ld + schunk * 8);
-            vreg[st][i] = *(const V8*)(vbase + (long long)row * kv_ld + schunk * 8);
+            for (int i = 0; i < CH; ++i) {
+                kreg[st][i] = *(GV8)(kt_ + soff[i]);
+                vreg[st][i] = *(GV8)(vt_ + soff[i]);
+            }
+        } else {
+            const int last = n_kv - 1 - t * KV_TILE;
+#pragma unroll
+            for (int i = 0; i < CH; ++i) {
+                const unsigned o = (unsigned)(min(srow + RSTEP * i, last) * kv_ld + schunk * 8) * (unsigned)sizeof(T);
+                kreg[st][i] = *(GV8)(kt_ + o);
+                vreg[st][i] = *(GV8)(vt_ + o);
+            }
         }
     };
     auto lstore = [&](auto SET, int buf) {
@@ -106,6 +140,11 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const T* __restrict__ q, 
     }
     lstore(Set0{}, 0);
     __syncthreads();
+    // vmcnt(0) alone, as a builtin so that the compiler's wait tracker sees it: the Q fragments are complete on every path into the
+    // tile loop (the scheduler issues their loads behind tile 0's, and the non-staging waves wait for nothing above).  Without it
+    // the Q waits land INSIDE the loop, between the prefetch loads and the first MFMAs, where from the second tile on a vmcnt(0)
+    // also waits for the prefetch just issued (tests/test_attn_isa_cpu.py keeps it out).
+    __builtin_amdgcn_s_waitcnt(0x0F70);
 
     // V^T fragment addressing: 16-lane group G = lane>>4 = 2h + (r>>4); lane i of the group supplies the
     // address of V[row + (i>>2)][col + 4*(i&3)] and receives column i of those 4 rows.
@@ -123,10 +162,19 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const T* __restrict__ q, 
         const char* kt = smem + cur * BUF_BYTES;
         const char* vt = kt + K_BYTES;
 
+        // a 32-key block of the last tile that lies wholly beyond n_kv is skipped (wave-uniform): its weights are exactly 0, so the
+        // result is the same bits without its 4 + 4 MFMAs and 16 exponentials (cross-attention to 77 keys: keys 96..127).  The
+        // causal mask never skips.
+        auto live = [&](int kb) {
+            if constexpr (decltype(TAIL)::value) return __builtin_amdgcn_readfirstlane(t * KV_TILE + (kb0 + kb) * 32) < n_kv;
+            else return true;
+        };
+
         // ---- S^T[key][q] for the 64 keys of this tile: 2 key blocks x 4 k-steps over d
         f32x16 sacc[NKB];
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {
+            if (!live(kb)) continue;
             const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
@@ -137,7 +185,8 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const T* __restrict__ q, 
         // online softmax on the RAW scores: the scale (and log2 e) rides in the exp2 argument as one FMA per element
         float mx = -INFINITY;
 #pragma unroll
-        for (int kb = 0; kb < NKB; ++kb)
+        for (int kb = 0; kb < NKB; ++kb) {
+            if (!live(kb)) continue;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 if constexpr (decltype(TAIL)::value) {        // mask keys beyond n_kv (last, partial tile only)
@@ -146,6 +195,7 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const T* __restrict__ q, 
                 }
                 mx = fmaxf(mx, sacc[kb][i]);
             }
+        }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         const float m_new = fmaxf(m_run, mx);
         const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2e);
@@ -153,17 +203,39 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const T* __restrict__ q, 
         m_run = m_new;
         const float mb = m_new * scale_log2e;
         float rs = 0.f;
+        // key-split forms: the exp2 arguments and the row sum as float pairs (v_pk_fma_f32 / v_pk_add_f32).  Each argument is the same
+        // single-rounded FMA; the row sum becomes two interleaved partial sums.  Measured at 4096 keys: 12 waves 79.2 -> 75.2 us, but
+        // 4 waves (32 scores per lane and tile) 3358 -> 3416 us at B_eff 128, so those keep one scalar per instruction.
+        constexpr bool PACKED = KSPLIT == 2;
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        f32x2 rs2 = {0.f, 0.f};
         V8 pf[NKB][2];
 #pragma unroll
-        for (int kb = 0; kb < NKB; ++kb)
+        for (int kb = 0; kb < NKB; ++kb) {
+            if (!live(kb)) continue;
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[kb][8 * s2 + j], scale_log2e, -mb));
-                    rs += pv;
-                    pf[kb][s2][j] = from_f32<T>(pv);
+                for (int j = 0; j < 8; j += 2) {
+                    if constexpr (PACKED) {
+                        const f32x2 sv = {sacc[kb][8 * s2 + j], sacc[kb][8 * s2 + j + 1]};
+                        const f32x2 sc2 = {scale_log2e, scale_log2e}, nmb2 = {-mb, -mb};
+                        const f32x2 a = __builtin_elementwise_fma(sv, sc2, nmb2);
+                        const f32x2 p2 = {__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
+                        rs2 += p2;
+                        pf[kb][s2][j] = from_f32<T>(p2[0]);
+                        pf[kb][s2][j + 1] = from_f32<T>(p2[1]);
+                    } else {
+#pragma unroll
+                        for (int e = j; e < j + 2; ++e) {
+                            const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[kb][8 * s2 + e], scale_log2e, -mb));
+                            rs += pv;
+                            pf[kb][s2][e] = from_f32<T>(pv);
+                        }
+                    }
                 }
+        }
+        if constexpr (PACKED) rs = rs2[0] + rs2[1];
         l_run = l_run * alpha + rs;
         if (__builtin_amdgcn_ballot_w64(grew) != 0) {         // wave-uniform: no row max moved -> alpha == 1 everywhere
 #pragma unroll
@@ -174,7 +246,8 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const T* __restrict__ q, 
 
         // ---- O^T[d][q] += V^T P^T
 #pragma unroll
-        for (int kb = 0; kb < NKB; ++kb)
+        for (int kb = 0; kb < NKB; ++kb) {
+            if (!live(kb)) continue;
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 const int base_row = (kb0 + kb) * 32 + 16 * s2 + tr_row;
@@ -192,6 +265,7 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const T* __restrict__ q, 
                     oacc[d] = Op<T>::mfma32(vf, pf[kb][s2], oacc[d]);
                 }
             }
+        }
 
         if (t + 1 < ntiles) lstore(Next{}, cur ^ 1);
         __syncthreads();
@@ -303,6 +377,7 @@ extern "C" int idb_attention(const void* q, int32_t q_ld, const void* k, const v
     IDB_REQUIRE(batch > 0 && heads > 0 && n_q > 0 && n_kv > 0 && n_kv_alloc >= n_kv, "idb_attention: bad dims");
     IDB_REQUIRE(q_ld % 8 == 0 && kv_ld % 8 == 0 && out_ld % 4 == 0, "idb_attention: row strides must be multiples of 8 (q,kv) / 4 (out)");
     IDB_REQUIRE(q_ld >= heads * 64 && kv_ld >= heads * 64 && out_ld >= heads * 64, "idb_attention: row stride < heads*64");
+    IDB_REQUIRE(kv_ld < (1 << 24), "idb_attention: kv_ld too large (a 64-row K/V tile must span less than 2^31 bytes)");
     IDB_REQUIRE(batch <= 65535 && heads <= 65535, "idb_attention: grid too large");
     IDB_REQUIRE(!causal || n_q == n_kv, "idb_attention: causal needs n_q == n_kv");
     const float sl2 = scale * 1.44269504088896340736f;
