@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("IDB_LIB") or os.path.join(_HERE, "libidb_kernels.so")
 
 IDB_BF16, IDB_F16, IDB_F32 = 0, 1, 2
 IDB_MAX_SRC = 4
+IDB_PLMS_SLOTS = 4
+IDB_PLMS_KEEP, IDB_PLMS_SAVE, IDB_PLMS_RESTORE = 0, 1, 2
 IDB_PAIR_DIST2, IDB_PAIR_KNN, IDB_PAIR_PRDC, IDB_PAIR_NEAREST, IDB_PAIR_POLY = 0, 1, 2, 3, 4
 # the selected points of idb_verif_roc, in the order of its points / ints outputs
 IDB_VERIF_POINTS = ("eer_t2", "eer_t1", "fmr0", "fmr1000", "fmr100", "fmr20", "fmr10", "fnmr0", "fnmr100", "fnmr1000", "youden", "mcc", "first")
@@ -27,7 +29,7 @@ EXPORTS = [
     "idb_groupnorm_workspace_bytes", "idb_groupnorm", "idb_groupnorm_plan", "idb_layernorm", "idb_groupnorm_stats",
     "idb_attention", "idb_attention_plan", "idb_embed_tokens", "idb_softmax_rows",
     "idb_timestep_sinusoid", "idb_linear_f32", "idb_conv_in",
-    "idb_cfg_ddpm_step", "idb_postprocess",
+    "idb_cfg_ddpm_step", "idb_cfg_plms_step", "idb_postprocess",
     "idb_nhwc_to_nchw_f32", "idb_f32_nhwc_to_nchw", "idb_cast_f32", "idb_vae_sample", "idb_warp_affine_u8",
     "idb_crop_resize_area_u8", "idb_conv2d_f32", "idb_maxpool2d_f32", "idb_softmax_pairs_f32", "idb_nms_mask",
     "idb_quantize_fp8", "idb_pack_weight_fp8", "idb_gemm_fp8", "idb_groupnorm_fp8",
@@ -124,6 +126,7 @@ def load() -> C.CDLL:
         "idb_linear_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
         "idb_conv_in": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, i32, vp]),
         "idb_cfg_ddpm_step": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        "idb_cfg_plms_step": (C.c_int, [vp, vp, vp, vp, vp] + [i32] * 11 + [vp]),
         "idb_postprocess": (C.c_int, [vp, vp, vp, i64, vp]),
         "idb_nhwc_to_nchw_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
         "idb_f32_nhwc_to_nchw": (C.c_int, [vp, vp, i32, i32, i32, vp]),

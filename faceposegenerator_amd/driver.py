@@ -278,6 +278,36 @@ def generate(pipe, items: Sequence[WorkItem], embed_fn: Callable, cfg: PolicyCon
 
 
 # ---------------------------------------------------------------------------------------------------
+# prior-preservation class images (train_ID-Booth.py:548-592)
+# ---------------------------------------------------------------------------------------------------
+def generate_class_images(pipe, class_prompt: str, class_data_dir: str, num_class_images: int, sample_batch_size: int = 1,
+                          generator=None) -> List[str]:
+    """The host policy of train_ID-Booth.py:548-592: top `class_data_dir` up to `num_class_images` images of `class_prompt` with
+    the pipeline's DEFAULT call (the scheduler of the model directory, 50 steps, guidance 7.5, no negative prompt:
+    ``DiffusionPipeline.from_pretrained(dir)``).  Whatever the directory already holds counts; new files are named
+    ``{index + already_there}-{sha1 of the image bytes}.jpg`` with Pillow's default JPEG settings, `index` from 0 over the new
+    images, generated in batches of `sample_batch_size` with a short last batch.  Returns the paths written ([] when the directory
+    already holds enough).  The reference draws its latents from the global CUDA RNG, which nothing on this platform reproduces:
+    parity is defined on the CPU `generator` passed here, as everywhere else in this package."""
+    import hashlib
+    os.makedirs(class_data_dir, exist_ok=True)
+    cur = len(os.listdir(class_data_dir))
+    if cur >= num_class_images:
+        return []
+    if sample_batch_size < 1:
+        raise ValueError(f"sample_batch_size must be positive, got {sample_batch_size}")
+    num_new = num_class_images - cur
+    paths: List[str] = []
+    for first in range(0, num_new, sample_batch_size):
+        images = pipe([class_prompt] * min(sample_batch_size, num_new - first), generator=generator).images
+        for k, image in enumerate(images):
+            sha = hashlib.sha1(image.tobytes()).hexdigest()
+            paths.append(os.path.join(class_data_dir, f"{first + k + cur}-{sha}.jpg"))
+            image.save(paths[-1])
+    return paths
+
+
+# ---------------------------------------------------------------------------------------------------
 # sink (inference_ID-Booth.py:139-156; torchvision.utils.save_image / make_grid(nrow, padding=0))
 # ---------------------------------------------------------------------------------------------------
 def _write_png(job) -> str:

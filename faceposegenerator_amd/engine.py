@@ -24,7 +24,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -40,6 +40,18 @@ def _stream() -> int:
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
+
+
+def plms_slots(i: int) -> Tuple[int, int, Tuple[int, int, int], int]:
+    """What idb_cfg_plms_step does at PLMS loop index i: (write_slot, n_terms, (slot1, slot2, slot3), sample_mode).  Index 1 keeps
+    nothing (it averages the new prediction with ets[-1] and restarts from the sample saved at index 0), so the k-th kept
+    prediction (k = 0 at index 0, i - 1 from index 2 on) lives in slot k % 4 and term j reads slot (k - j) % 4; with
+    n_terms = min(k + 1, 4) no slot is read before it has been written."""
+    n = L.IDB_PLMS_SLOTS
+    if i == 1:
+        return -1, 2, (0, 0, 0), L.IDB_PLMS_RESTORE
+    k = 0 if i == 0 else i - 1
+    return k % n, min(k + 1, n), tuple((k - j) % n for j in (1, 2, 3)), L.IDB_PLMS_SAVE if i == 0 else L.IDB_PLMS_KEEP
 
 
 class Arena:
@@ -1078,7 +1090,7 @@ class HipEngine:
     # ------------------------------------------------------------------------------------
     # sampling loop (StableDiffusionPipeline.__call__ steps 3-5)
     # ------------------------------------------------------------------------------------
-    def _sample_body(self, ctx_f32, noise, coefs, tp, lat, eps, steps, rep, n_ctx, vpred, trace=None, hist=None) -> None:
+    def _sample_body(self, ctx_f32, noise, coefs, tp, lat, eps, steps, rep, n_ctx, vpred, trace=None, hist=None, plms: bool = False) -> None:
         """One whole sampling loop on the current stream; every buffer is passed in, so the same
         code runs eagerly or under HIP-graph capture."""
         B = noise.shape[1]
@@ -1087,7 +1099,7 @@ class HipEngine:
         self._pinned.clear()
         self._rep = rep
         lat.copy_(noise[0])                                  # init_noise_sigma = 1
-        if hist is not None:
+        if hist is not None and not plms:
             hist.zero_()                                     # multistep solver: x0 history (coefficient 0 on the first step)
         ctx = self.arena.alloc(tuple(ctx_f32.shape), self.tdt)
         L.check(self.lib.idb_cast_f32(ctx_f32.data_ptr(), ctx.data_ptr(), ctx_f32.numel(), self.dt, _stream()), "idb_cast_f32")
@@ -1099,29 +1111,46 @@ class HipEngine:
         self.arena.free(ctx)
         for i in range(steps):
             self.unet_nhwc(lat, rep, (tp, i * self.tproj_total, 0), kv, n_ctx, eps_out=eps)
-            if hist is None:                                 # DDPM: third operand = this step's variance noise
-                third, x0_out = noise[i + 1].data_ptr(), None
-            else:                                            # DPM-Solver++ 2M: third operand = previous x0 prediction; keep this one
-                third, x0_out = hist[(i + 1) & 1].data_ptr(), hist[i & 1].data_ptr()
-            L.check(self.lib.idb_cfg_ddpm_step(eps.data_ptr(), lat.data_ptr(), third, coefs[i].data_ptr(),
-                                               x0_out, B, lat.shape[1], h * w_, int(rep == 2), int(vpred), _stream()),
-                    "idb_cfg_ddpm_step")
+            if plms:                                         # PLMS: eps history and the saved sample live in hist
+                self._plms_step(eps, lat, hist, coefs[i], i, B, h * w_, rep, vpred)
+            else:
+                if hist is None:                             # DDPM: third operand = this step's variance noise
+                    third, x0_out = noise[i + 1].data_ptr(), None
+                else:                                        # DPM-Solver++ 2M: third operand = previous x0 prediction; keep this one
+                    third, x0_out = hist[(i + 1) & 1].data_ptr(), hist[i & 1].data_ptr()
+                L.check(self.lib.idb_cfg_ddpm_step(eps.data_ptr(), lat.data_ptr(), third, coefs[i].data_ptr(),
+                                                   x0_out, B, lat.shape[1], h * w_, int(rep == 2), int(vpred), _stream()),
+                        "idb_cfg_ddpm_step")
             if trace is not None:
                 trace.append((eps.clone(), lat.clone()))
 
+    def _plms_step(self, eps, lat, hist, coef, i: int, B: int, hw: int, rep: int, vpred: bool) -> None:
+        """Loop index i of PNDMScheduler's PLMS in one launch.  hist: [IDB_PLMS_SLOTS + 1, B, C, h, w], the ring of guided eps
+        (``plms_slots``) followed by the sample saved at index 0."""
+        write, terms, slots, mode = plms_slots(i)
+        L.check(self.lib.idb_cfg_plms_step(eps.data_ptr(), lat.data_ptr(), hist.data_ptr(), hist[L.IDB_PLMS_SLOTS].data_ptr(),
+                                           coef.data_ptr(), B, lat.shape[1], hw, rep, int(vpred), write, terms, *slots, mode,
+                                           _stream()), "idb_cfg_plms_step")
+
     def sample(self, prompt_embeds: torch.Tensor, negative_prompt_embeds: Optional[torch.Tensor], noise: torch.Tensor,
                timesteps: Sequence[int], coefs: torch.Tensor, vpred: bool = False, use_graph: bool = False,
-               trace: Optional[list] = None, multistep: bool = False) -> torch.Tensor:
+               trace: Optional[list] = None, multistep: Union[bool, str] = False) -> torch.Tensor:
         """noise: [steps+1, B, 4, h, w] fp32 on device (noise[0] = initial latents); coefs: [steps, 6] fp32 on
         device (sqrt_a, sqrt_b, c_x0, c_x, sigma, guidance_scale).  CFG is on iff negative_prompt_embeds is
         given.  Returns final latents [B,4,h,w] fp32.  ``trace`` collects (eps [2B*hw,4], latents) per step.
         multistep (DPM-Solver++ 2M, train_ID-Booth.py:155): noise is [1, B, 4, h, w] (initial latents only) and the fifth
-        coefficient multiplies the previous step's x0 prediction instead of fresh noise."""
+        coefficient multiplies the previous step's x0 prediction instead of fresh noise.
+        multistep="plms" (PNDMScheduler, the default scheduler of train_ID-Booth.py:562-583): noise is [1, B, 4, h, w] as well,
+        timesteps are the n + 1 PLMS entries and coefs is [n + 1, 9]: PNDMScheduler.step_coefficients(i) + guidance_scale."""
+        plms = multistep == "plms"
+        if not plms and not isinstance(multistep, bool):
+            raise ValueError(f"multistep must be False, True or 'plms', got {multistep!r}")
         steps = len(timesteps)
         B, lc, h, w_ = noise.shape[1:]
         cfg_on = negative_prompt_embeds is not None
         rep = 2 if cfg_on else 1
         n_ctx = prompt_embeds.shape[1]
+        n_hist = L.IDB_PLMS_SLOTS + 1 if plms else 2          # PLMS: four eps slots and the saved sample; DPM-Solver++: two x0 slots
         ctx_f32 = torch.cat([negative_prompt_embeds, prompt_embeds]) if cfg_on else prompt_embeds   # uncond FIRST
         ctx_f32 = ctx_f32.to(self.device).float().reshape(rep * B * n_ctx, -1).contiguous()
         noise = noise.to(self.device).float().contiguous()
@@ -1131,8 +1160,8 @@ class HipEngine:
         if not use_graph or trace is not None:
             lat = torch.empty((B, lc, h, w_), dtype=torch.float32, device=self.device)
             eps = torch.empty((rep * B * h * w_, self.ucfg.out_channels), dtype=torch.float32, device=self.device)
-            hist = torch.empty((2, B, lc, h, w_), dtype=torch.float32, device=self.device) if multistep else None
-            self._sample_body(ctx_f32, noise, coefs, tp, lat, eps, steps, rep, n_ctx, vpred, trace, hist)
+            hist = torch.empty((n_hist, B, lc, h, w_), dtype=torch.float32, device=self.device) if multistep else None
+            self._sample_body(ctx_f32, noise, coefs, tp, lat, eps, steps, rep, n_ctx, vpred, trace, hist, plms)
             return lat
         if not hasattr(self, "_graphs"):
             self._graphs = {}
@@ -1142,11 +1171,11 @@ class HipEngine:
             ent = {"ctx": ctx_f32.clone(), "noise": noise.clone(), "coefs": coefs.clone(), "tp": tp.clone(),
                    "lat": torch.empty((B, lc, h, w_), dtype=torch.float32, device=self.device),
                    "eps": torch.empty((rep * B * h * w_, self.ucfg.out_channels), dtype=torch.float32, device=self.device)}
-            # every buffer the captured graph references lives in `ent` (the multistep x0 history too: a local here would go
-            # back to the caching allocator while replays keep writing through its address)
-            ent["hist"] = torch.empty((2, B, lc, h, w_), dtype=torch.float32, device=self.device) if multistep else None
+            # every buffer the captured graph references lives in `ent` (the multistep x0 / PLMS eps history too: a local here
+            # would go back to the caching allocator while replays keep writing through its address)
+            ent["hist"] = torch.empty((n_hist, B, lc, h, w_), dtype=torch.float32, device=self.device) if multistep else None
             args = (ent["ctx"], ent["noise"], ent["coefs"], ent["tp"], ent["lat"], ent["eps"], steps, rep, n_ctx, vpred, None,
-                    ent["hist"])
+                    ent["hist"], plms)
             self._sample_body(*args)                     # eager warm-up: allocates every arena block, sets func attributes
             torch.cuda.synchronize(self.device)
             graph = torch.cuda.CUDAGraph()

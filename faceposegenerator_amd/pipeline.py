@@ -26,7 +26,7 @@ import torch
 
 from . import spec as S
 from . import weights as W
-from .scheduler import DDPMScheduler, DPMSolverMultistepScheduler
+from .scheduler import DDPMScheduler, DPMSolverMultistepScheduler, PNDMScheduler
 
 
 class _range:
@@ -170,6 +170,7 @@ class StableDiffusionPipeline:
     # ---- construction -----------------------------------------------------------------
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str, torch_dtype=None, **kw) -> "StableDiffusionPipeline":
+        """Always installs a DDPMScheduler; ``DiffusionPipeline.from_pretrained`` installs the scheduler the directory names."""
         root = pretrained_model_name_or_path
         if not os.path.isdir(root):
             raise FileNotFoundError(f"{root!r} is not a local directory; model names cannot be resolved offline "
@@ -362,7 +363,8 @@ class StableDiffusionPipeline:
         sch = self.scheduler
         sch.set_timesteps(num_inference_steps)
         timesteps = sch.timesteps.tolist()
-        multistep = isinstance(sch, DPMSolverMultistepScheduler)         # deterministic solver: initial latents only
+        plms = isinstance(sch, PNDMScheduler)
+        multistep = plms or isinstance(sch, DPMSolverMultistepScheduler)  # deterministic solvers: initial latents only
         if noise is None:
             if latents is not None and not multistep:
                 # upstream prepare_latents draws nothing when `latents` is given: the generator's first draw is step 0's noise
@@ -376,6 +378,7 @@ class StableDiffusionPipeline:
             noise[0] = latents.float().cpu() * sch.init_noise_sigma
         if multistep:
             noise = noise[:1]
+            # per loop index (PLMS: n + 1 of them, one UNet call and one time-embedding row each), guidance appended
             coefs = torch.tensor([list(sch.step_coefficients(i)) + [float(guidance_scale)] for i in range(len(timesteps))],
                                  dtype=torch.float32)
         else:
@@ -383,7 +386,7 @@ class StableDiffusionPipeline:
         with _range("idb:sampling_loop"):
             lat = eng.sample(prompt_embeds, negative_prompt_embeds if do_cfg else None, noise.to(self.device), timesteps,
                              coefs.to(self.device), vpred=(sch.config.prediction_type == "v_prediction"),
-                             use_graph=self.use_graph, multistep=multistep)
+                             use_graph=self.use_graph, multistep="plms" if plms else multistep)
         if output_type == "latent":
             images = lat
         else:
@@ -401,3 +404,23 @@ class StableDiffusionPipeline:
         if not return_dict:
             return (images, None)
         return StableDiffusionPipelineOutput(images=images, nsfw_content_detected=None)
+
+
+class DiffusionPipeline(StableDiffusionPipeline):
+    """``diffusers.DiffusionPipeline`` as the reference spells it (train_ID-Booth.py:562, :1211): the same pipeline, but
+    ``from_pretrained(dir)`` installs the scheduler that ``scheduler/scheduler_config.json`` names, as upstream does.  For SD-2.1
+    that is PNDMScheduler, so ``DiffusionPipeline.from_pretrained(dir)(prompt)`` is the default call: PLMS, 50 steps, guidance 7.5."""
+    SCHEDULERS = {"PNDMScheduler": PNDMScheduler, "DDPMScheduler": DDPMScheduler,
+                  "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler}
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path: str, torch_dtype=None, **kw) -> "DiffusionPipeline":
+        root = pretrained_model_name_or_path
+        if not os.path.isdir(root):
+            return super().from_pretrained(root, torch_dtype, **kw)             # raises: not a local directory
+        name = W._read_json(os.path.join(root, "scheduler", "scheduler_config.json")).get("_class_name")
+        if name not in cls.SCHEDULERS:
+            raise ValueError(f"scheduler class {name!r} is not supported (one of {sorted(cls.SCHEDULERS)})")
+        pipe = super().from_pretrained(root, torch_dtype, **kw)
+        pipe.scheduler = cls.SCHEDULERS[name].from_pretrained(pretrained_model_name_or_path, subfolder="scheduler")
+        return pipe

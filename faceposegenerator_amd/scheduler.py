@@ -6,12 +6,16 @@ Reference call sites: ``DDPMScheduler.from_pretrained(model, subfolder="schedule
 (:147-153, :1011, :1055).  Restated from diffusers 0.32.2 ``schedulers/scheduling_ddpm.py``
 (SURVEY.md §3.3): scaled_linear betas, leading spacing, steps_offset, fixed_small variance, no clipping.
 
+``DPMSolverMultistepScheduler`` (the reference's validation sampler, :155) and ``PNDMScheduler`` (PLMS, the scheduler SD-2.1's
+directory names and the default ``DiffusionPipeline`` call runs, :562-583, :1211) follow the same pattern below.
+
 Tables and coefficients are host fp32 (30 scalars).  ``step`` on GPU tensors runs the fused HIP
 kernel ``idb_cfg_ddpm_step``; the pipeline's sampling loop calls the same kernel directly with CFG
 fused in.
 """
 from __future__ import annotations
 
+import os
 from dataclasses import asdict
 from types import SimpleNamespace
 from typing import List, Optional, Tuple, Union
@@ -267,6 +271,156 @@ class DPMSolverMultistepScheduler:
         if not return_dict:
             return (prev,)
         return DDPMSchedulerOutput(prev, x0)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        ac = self.alphas_cumprod.to(original_samples.device)
+        sa, sb = (ac[timesteps] ** 0.5).flatten(), ((1 - ac[timesteps]) ** 0.5).flatten()
+        while sa.ndim < original_samples.ndim:
+            sa, sb = sa.unsqueeze(-1), sb.unsqueeze(-1)
+        return sa * original_samples + sb * noise
+
+    def __len__(self):
+        return self._cfg.num_train_timesteps
+
+
+class PNDMSchedulerOutput:
+    def __init__(self, prev_sample):
+        self.prev_sample = prev_sample
+
+    def __iter__(self):
+        return iter((self.prev_sample,))
+
+
+class PNDMScheduler:
+    """PLMS, the scheduler SD-2.1's model directory names (``scheduler/scheduler_config.json``: ``_class_name`` "PNDMScheduler",
+    ``skip_prk_steps`` true, ``set_alpha_to_one`` false, ``steps_offset`` 1) and therefore the one a default
+    ``DiffusionPipeline.from_pretrained(model)(prompt)`` samples with: the reference's class images (train_ID-Booth.py:562-583) and
+    its validation pipeline before the scheduler is swapped (:1211).
+
+    [UPSTREAM], parity unpinned: restated from diffusers 0.32.2 ``schedulers/scheduling_pndm.py`` (``step_plms`` and
+    ``_get_prev_sample``); diffusers cannot be imported here, so tests/test_pndm_cpu.py pins the algorithm analytically (DDIM
+    equivalences, known timesteps and coefficients) and against an independent float64 restatement.
+
+    Deliberate deviation: a config without ``skip_prk_steps`` / ``set_alpha_to_one`` takes SD-2.1's FILE values (True / False), not
+    upstream's class default ``skip_prk_steps=False``: another scheduler's ``.config`` carries neither key, and every SD directory
+    sets them this way.  ``skip_prk_steps=False`` (Runge-Kutta warm-up steps) raises; no SD config uses it.
+
+    n inference steps make n + 1 UNet calls (the second timestep is visited twice).  Every update is
+    x_prev = c_sample x - c_eps m with m a fixed linear combination of the current and up to three past eps predictions;
+    ``step_coefficients(i)`` gives the scalars of loop index i and the device step is ``idb_cfg_plms_step``
+    (engine.HipEngine.sample(multistep="plms")).  ``step`` is the stateful host form of the same update, in fp32."""
+    order = 1
+    # history weights by loop index: [current, ets[-2], ets[-3], ets[-4]]; index 1 averages the new prediction with ets[-1]
+    _WEIGHTS = ((1.0, 0.0, 0.0, 0.0), (0.5, 0.5, 0.0, 0.0), (1.5, -0.5, 0.0, 0.0), (23 / 12, -16 / 12, 5 / 12, 0.0),
+                (55 / 24, -59 / 24, 37 / 24, -9 / 24))
+
+    def __init__(self, config: S.SchedulerConfig = S.SD21_SCHED, skip_prk_steps: bool = True, set_alpha_to_one: bool = False):
+        if config.beta_schedule != "scaled_linear":
+            raise ValueError(f"beta_schedule {config.beta_schedule!r} is not supported (SD-2.x uses scaled_linear)")
+        if config.timestep_spacing != "leading":
+            raise ValueError("only timestep_spacing='leading' is supported")
+        if config.prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(f"prediction_type {config.prediction_type!r} is not supported")
+        if not skip_prk_steps:
+            raise ValueError("skip_prk_steps=False (Runge-Kutta warm-up steps) is not supported; SD configs set it to true")
+        self._cfg = config
+        self.config = SimpleNamespace(**asdict(config), skip_prk_steps=True, set_alpha_to_one=bool(set_alpha_to_one))
+        betas = torch.linspace(config.beta_start ** 0.5, config.beta_end ** 0.5, config.num_train_timesteps, dtype=torch.float32) ** 2
+        self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
+        self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
+        self.init_noise_sigma = 1.0
+        self.num_inference_steps: Optional[int] = None
+        self.timesteps = torch.arange(config.num_train_timesteps - 1, -1, -1, dtype=torch.int64)
+        self._reset()
+
+    def _reset(self):
+        self.ets: List[torch.Tensor] = []
+        self.counter = 0
+        self.cur_sample = None
+
+    @classmethod
+    def from_pretrained(cls, path: str, subfolder: Optional[str] = None, **kw) -> "PNDMScheduler":
+        """Local directory only (model names cannot be resolved offline)."""
+        p = os.path.join(path, subfolder) if subfolder else path
+        d = W._read_json(os.path.join(p, "scheduler_config.json"))
+        return cls(W.load_scheduler_config(path, subfolder), skip_prk_steps=d.get("skip_prk_steps", True),
+                   set_alpha_to_one=d.get("set_alpha_to_one", False))
+
+    @classmethod
+    def from_config(cls, config, **kw) -> "PNDMScheduler":
+        """Accepts another scheduler's ``.config`` (namespace / dict) or a SchedulerConfig; keys PLMS does not use are ignored."""
+        own = {k: kw.pop(k) for k in ("skip_prk_steps", "set_alpha_to_one") if k in kw}
+        if isinstance(config, S.SchedulerConfig):
+            return cls(config, **own)
+        d = dict(vars(config)) if not isinstance(config, dict) else dict(config)
+        d.update(kw)
+        keys = S.SchedulerConfig.__dataclass_fields__.keys()
+        own = {**{k: d[k] for k in ("skip_prk_steps", "set_alpha_to_one") if k in d}, **own}
+        return cls(S.SchedulerConfig(**{k: v for k, v in d.items() if k in keys}), **own)
+
+    def set_timesteps(self, num_inference_steps: int, device=None) -> None:
+        n_train = self._cfg.num_train_timesteps
+        if not 0 < num_inference_steps <= n_train:
+            raise ValueError(f"num_inference_steps {num_inference_steps} must be in 1..{n_train}")
+        self.num_inference_steps = num_inference_steps
+        ratio = n_train // num_inference_steps
+        _t = [int(round(i * ratio)) + self._cfg.steps_offset for i in range(num_inference_steps)]
+        # upstream (skip_prk_steps): concat(_t[:-1], _t[-2:-1], _t[-1:])[::-1], the second-to-last ascending entry doubled
+        self.timesteps = torch.tensor((_t[:-1] + _t[-2:-1] + _t[-1:])[::-1], dtype=torch.int64)
+        self._reset()
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def _times(self, i: int) -> Tuple[int, int]:
+        """(t, t_prev) the update of loop index i is taken between."""
+        r = self._cfg.num_train_timesteps // self.num_inference_steps
+        t = int(self.timesteps[i])
+        return (t + r, t) if i == 1 else (t, t - r)
+
+    def step_coefficients(self, i: int):
+        """(w0, w1, w2, w3, sqrt(abar_t), sqrt(1-abar_t), c_sample, c_eps) of loop index i in fp32:
+        m = w0 e + w1 ets[-2] + w2 ets[-3] + w3 ets[-4] (index 1: w1 multiplies ets[-1], e is not kept),
+        v_prediction: m = sqrt(abar_t) m + sqrt(1-abar_t) x;  x_prev = c_sample x - c_eps m.
+        The scalars are formed in float64 from upstream's float32 ``alphas_cumprod`` table and rounded once."""
+        if self.num_inference_steps is None or not 0 <= i < len(self.timesteps):
+            raise ValueError("call set_timesteps first / loop index out of range")
+        t, t_prev = self._times(i)
+        a = float(self.alphas_cumprod[t])
+        a_prev = float(self.alphas_cumprod[t_prev]) if t_prev >= 0 else float(self.final_alpha_cumprod)
+        c_sample = (a_prev / a) ** 0.5
+        c_eps = (a_prev - a) / (a * (1 - a_prev) ** 0.5 + (a * (1 - a) * a_prev) ** 0.5)
+        f = lambda v: float(torch.tensor(v, dtype=torch.float32))
+        return tuple(f(v) for v in self._WEIGHTS[min(i, 4)] + (a ** 0.5, (1 - a) ** 0.5, c_sample, c_eps))
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None, return_dict: bool = True, **kw):
+        i = self.counter
+        if self.num_inference_steps is None or i >= len(self.timesteps):
+            raise ValueError("call set_timesteps first / too many steps")
+        if int(timestep) != int(self.timesteps[i]):
+            raise ValueError(f"step {i} expects timestep {int(self.timesteps[i])}, got {int(timestep)}")
+        w0, w1, w2, w3, sa, sb, c_sample, c_eps = self.step_coefficients(i)
+        e, x = model_output.float(), sample.float()
+        if i != 1:
+            self.ets = self.ets[-3:] + [e]
+        if i == 0:
+            self.cur_sample = x
+            m = e
+        elif i == 1:
+            m = w0 * e + w1 * self.ets[-1]
+            x = self.cur_sample
+            self.cur_sample = None
+        else:
+            m = w0 * self.ets[-1]
+            for w, past in zip((w1, w2, w3), self.ets[-2::-1]):
+                m = m + w * past
+        if self._cfg.prediction_type == "v_prediction":
+            m = sa * m + sb * x
+        prev = c_sample * x - c_eps * m
+        self.counter += 1
+        if not return_dict:
+            return (prev,)
+        return PNDMSchedulerOutput(prev)
 
     def add_noise(self, original_samples, noise, timesteps):
         ac = self.alphas_cumprod.to(original_samples.device)

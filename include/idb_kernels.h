@@ -301,6 +301,29 @@ int idb_cfg_ddpm_step(const float* eps, float* latents, const float* noise, cons
                       float* x0_out, int32_t batch, int32_t channels, int32_t hw, int32_t cfg,
                       int32_t prediction_type, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K8b — classifier-free guidance + PNDMScheduler.step (PLMS, skip_prk_steps), fp32, one launch per step
+ * (train_ID-Booth.py:562-583, :1211: the pipeline's default scheduler for SD-2.1).  eps is
+ * [rep*B][HW][C] fp32 (uncond first; rep 1 = no guidance, 2 = CFG); latents are NCHW fp32, updated in place.
+ * hist: IDB_PLMS_SLOTS NCHW fp32 slots of past guided eps, saved: one NCHW fp32 sample, both owned by the caller.
+ * coef points at 9 floats on the DEVICE: {w0, w1, w2, w3, sqrt_alpha_bar_t, sqrt_beta_bar_t, c_sample, c_eps,
+ * guidance_scale}.  Per element: e = e_u + g (e_c - e_u); hist[write_slot] = e unless write_slot is -1;
+ * m = w0 e + w1 hist[slot1] + w2 hist[slot2] + w3 hist[slot3], the first n_terms (1..4) terms only: a slot past
+ * n_terms is never read, whatever its weight; x = latents (IDB_PLMS_KEEP), latents which are also copied to
+ * `saved` (IDB_PLMS_SAVE), or `saved` (IDB_PLMS_RESTORE); prediction_type 1: m = sqrt_alpha_bar m + sqrt_beta_bar x;
+ * latents = c_sample x - c_eps m.  Everything structural is a host integer (fixed when a graph is captured),
+ * every scalar is read on the device.  IDB_EINVAL on rep outside {1,2}, n_terms outside 1..4, a slot index
+ * outside its range or a slot both read and written.
+ * ------------------------------------------------------------------------------------------ */
+#define IDB_PLMS_SLOTS 4
+#define IDB_PLMS_KEEP 0
+#define IDB_PLMS_SAVE 1
+#define IDB_PLMS_RESTORE 2
+int idb_cfg_plms_step(const float* eps, float* latents, float* hist, float* saved, const float* coef,
+                      int32_t batch, int32_t channels, int32_t hw, int32_t rep, int32_t prediction_type,
+                      int32_t write_slot, int32_t n_terms, int32_t slot1, int32_t slot2, int32_t slot3,
+                      int32_t sample_mode, void* stream);
+
 /* K10 — VaeImageProcessor.postprocess + save_image quantisation:
  * x [B][HW][C] fp32 -> img01 = clamp(x/2+0.5,0,1) (fp32 NHWC, may be NULL) and u8 = floor(255*img01+0.5). */
 int idb_postprocess(const float* x, float* img01, uint8_t* u8, int64_t count, void* stream);
