@@ -343,6 +343,72 @@ __device__ __forceinline__ void idb_patch_seek(const GemmParams& p, int g, int& 
     t = g - c * p.src[s].taps;
 }
 
+// GN = true pieces shared by the transforming patch loaders and the MFMA waves that help with the first patch (below).
+// {sum, sumsq} partials of eight groups (pw * 8 ..), 8 lanes per group: loads only
+__device__ __forceinline__ void idb_gn_part_load(const GemmParams& p, int b0, int pw, int lane, f32x2 (&pv)[8]) {
+    const int G = p.gn_in_groups;
+    const int g = min(pw * 8 + (lane >> 3), G - 1), sub = lane & 7;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int ch = min(sub + 8 * u, p.gn_in_chunks - 1);
+        pv[u] = *(const f32x2*)(p.gn_in_part + (((long long)b0 * p.gn_in_chunks + ch) * G + g) * 2);
+    }
+}
+
+// {mean, rstd} of those groups into gst: the pixel-chunk partials are added in gn_apply_kernel's order
+__device__ __forceinline__ void idb_gn_part_finish(const GemmParams& p, float2* gst, int pw, int lane, const f32x2 (&pv)[8]) {
+    const int G = p.gn_in_groups, cpg = p.gn_in_c / G;
+    const int g = min(pw * 8 + (lane >> 3), G - 1), sub = lane & 7;
+    float a = 0.f, q = 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        if (sub + 8 * u < p.gn_in_chunks) {
+            a += pv[u][0];
+            q += pv[u][1];
+        }
+    }
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) {
+        a += __shfl_xor(a, o, 64);
+        q += __shfl_xor(q, o, 64);
+    }
+    if (pw * 8 + (lane >> 3) < G && sub == 0) {
+        const double cnt = (double)p.HW * cpg;
+        const double mean = (double)a / cnt;
+        double var = (double)q / cnt - mean * mean;
+        if (var < 0.0) var = 0.0;
+        gst[g] = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)p.gn_in_eps)));
+    }
+}
+
+// k = rstd * gamma, h = beta - mean * k of the 8 channels from ch0.  The group of a channel is ch / cpg as ONE v_mul_hi_u32 with
+// rcpg = ceil(2^32 / cpg) (exact for ch * cpg < 2^32; cpg = 1 has no such reciprocal in 32 bits): eight integer divisions by a run-time
+// value were some 250 VALU instructions, in front of the first patch and in one K-step interval of every chunk
+__device__ __forceinline__ void idb_gn_coeffs(const float2* gst, int ch0, int cpg, unsigned rcpg, f32x4 g0v, f32x4 g1v, f32x4 b0v, f32x4 b1v, float (&kk)[8],
+                                              float (&hh)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float2 st = gst[cpg == 1 ? ch0 + e : (int)__umulhi((unsigned)(ch0 + e), rcpg)];
+        kk[e] = st.y * (e < 4 ? g0v[e] : g1v[e - 4]);
+        hh[e] = (e < 4 ? b0v[e] : b1v[e - 4]) - st.x * kk[e];
+    }
+}
+
+// y = silu(x * k + h) in fp32, one rounding; a padding pixel (ok = false: its load was zero-filled) stays zero
+template <typename T>
+__device__ __forceinline__ typename Op<T>::v8 idb_gn_norm8(typename Op<T>::v8 r, bool ok, int silu, const float (&kk)[8], const float (&hh)[8]) {
+    typename Op<T>::v8 o = r;
+    if (ok) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float y = to_f32<T>(r[e]) * kk[e] + hh[e];
+            if (silu) y = silu_f(y);
+            o[e] = from_f32<T>(y);
+        }
+    }
+    return o;
+}
+
 // MF = 4: 256-row tiles, 3-stage weight ring (large grids).  MF = 1 / 2: 64- / 128-row tiles, 4-stage ring, split-K by whole chunks
 // (the one-workgroup-per-CU plans of the batch-1 UNet): the patch is 3-4 image rows there, the saving is the 9x smaller activation
 // stream of a K-step whose weight stream is unchanged.
@@ -401,14 +467,64 @@ __global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const Ge
     const int nimg = p.HW >= BM ? 1 : BM / p.HW;
     const int RI = BM / W / nimg;                              // tile rows per image
 
+    // GN, the prologue (everything in front of the first MFMA) runs on all twelve non-weight waves:
+    //   * MFMA waves 0-3 load the producer's partial sums at once and turn them into {mean, rstd} per group (gst) in front of barrier S,
+    //     while the patch loaders work out their patch addresses; nothing that does not need the statistics waits for them — the raw
+    //     first patch and gamma / beta of the first chunk are requested before any wait, so ONE memory round trip is exposed;
+    //   * behind barrier S the first patch is normalised by all twelve: of its NU eight-pixel units the patch loaders keep the first LI of
+    //     their sweep (unit i * PL + pw, i < LI), MFMA wave w takes units PL * LI + w * NH + [0, NH), fetched raw by that wave in front of
+    //     barrier S: 2-3 units per wave instead of 7-9 on four.
+    // Barriers per role (a barrier that one wave misses hangs the workgroup): MFMA waves S + 1 (in front of the K loop) + (nk - 1) (in it),
+    // weight loaders S + nk, patch loaders S + the sum over their chunks of 1 + (n - 1) = S + nk: S + nk each, as before.  The first K
+    // barrier publishes patch buffer 0, so every wave that stored to it has lgkmcnt(0) in front of that barrier; the stores of the loaders
+    // (units < PL * LI) and of the MFMA waves are disjoint, and buffer 0 is next written behind the first barrier of the second chunk.
+    constexpr int NU = PP_PAD / 8;
+    constexpr int LI = (NU + 11) / 12;
+    constexpr int NH = GN ? (NU - PL * LI) / 8 : 1;
+    static_assert(!GN || (PL * LI + 8 * NH == NU && LI <= NPI), "first-patch split over 4 + 8 waves");
+    [[maybe_unused]] V8 hraw[NH];                              // MFMA waves: their raw units of the first patch,
+    [[maybe_unused]] bool hok[NH];                             // inside the image?
+    [[maybe_unused]] f32x4 hg0, hg1, hb0, hb1;                 // gamma / beta of their 8 channels of the first chunk
+    [[maybe_unused]] f32x2 hpv[8];                             // waves 0-3: the partial sums of eight groups
+    [[maybe_unused]] int hch0 = 0, hcpg = 1;
+    [[maybe_unused]] unsigned hrcpg = 0;
+
     if constexpr (GN) {
-        if (wave >= 10) {
+        const int q8 = lane >> 3;
+        const int b0 = m0 / p.HW, y0 = (m0 - b0 * p.HW) / W;
+        const int G = p.gn_in_groups, cpg = p.gn_in_c / G;
+        const unsigned rcpg = 0xFFFFFFFFu / (unsigned)cpg + 1u;   // ceil(2^32 / cpg) for cpg > 1 (idb_gn_coeffs)
+        const int co = (lane & 7) ^ q8;                        // this lane's channel octet inside every chunk (pixel q has q & 7 == q8)
+        const int PW = W + 2, PP = (RI + 2) * PW;
+        const unsigned rpw = (65536u + PW - 1) / PW;           // q / PW == (q * rpw) >> 16: q < 288, PW <= 66, so q * (rpw * PW - 65536) < 65536
+        // patch pixel q -> offset of this lane's 16 bytes in a source of C channels (IDB_OOB: outside the image or behind the patch's last pixel)
+        auto pix_voff = [&](int q, int C, bool& ok) -> unsigned {
+            const int pr = (int)(((unsigned)q * rpw) >> 16), px = q - pr * PW;
+            const int y = y0 + pr - 1, x = px - 1;
+            ok = q < PP && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
+            const int pix = (b0 * H + y) * W + x;
+            return ok ? (unsigned)pix * (unsigned)(C * 2) + (unsigned)(co * 16) : IDB_OOB;
+        };
+        if (wave < 8) {
+            // ---------------- MFMA waves, first half of their prologue: requests only ----------------
+            if (wave < 4) idb_gn_part_load(p, b0, wave, lane, hpv);
+            const GemmSrcK S = p.src[s0];
+            int cb = 0;
+            for (int q = 0; q < s0; ++q) cb += p.src[q].C;
+            hch0 = cb + c0 * 64 + co * 8;
+            hcpg = cpg;
+            hrcpg = rcpg;
+            hg0 = *(const f32x4*)(p.gn_in_gamma + hch0), hg1 = *(const f32x4*)(p.gn_in_gamma + hch0 + 4);
+            hb0 = *(const f32x4*)(p.gn_in_beta + hch0), hb1 = *(const f32x4*)(p.gn_in_beta + hch0 + 4);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)S.ptr, 0, S.bytes, IDB_RSRC_FLAGS);
+#pragma unroll
+            for (int j = 0; j < NH; ++j) {
+                const unsigned vo = pix_voff((PL * LI + wave * NH + j) * 8 + q8, S.C, hok[j]);
+                hraw[j] = __builtin_bit_cast(V8, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, (unsigned)c0 * 128u, 0));
+            }
+        } else if (wave >= 10) {
             // ---------------- transforming patch loaders (registers -> normalise -> LDS) ----------------
             const int pw = wave - 10;
-            const int q8 = lane >> 3;
-            const int b0 = m0 / p.HW, y0 = (m0 - b0 * p.HW) / W;
-            const int G = p.gn_in_groups, cpg = p.gn_in_c / G;
-            const int co = (lane & 7) ^ q8;                    // this lane's channel octet inside every chunk (pixel q has q & 7 == q8)
             unsigned voff[NPI];
             bool okp[NPI];
             int seg = -1, cb = 0;
@@ -416,17 +532,8 @@ __global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const Ge
             auto setup = [&](int s) {
                 const GemmSrcK S = p.src[s];
                 rs = __builtin_amdgcn_make_buffer_rsrc((void*)S.ptr, 0, S.bytes, IDB_RSRC_FLAGS);
-                const int PW = W + 2, RIh = RI + 2;
-                const int PP = RIh * PW;
 #pragma unroll
-                for (int i = 0; i < NPI; ++i) {
-                    const int q = (i * PL + pw) * 8 + q8;
-                    const int pr = q / PW, px = q - pr * PW;
-                    const int y = y0 + pr - 1, x = px - 1;
-                    okp[i] = q < PP && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-                    const int pix = (b0 * H + y) * W + x;
-                    voff[i] = okp[i] ? (unsigned)pix * (unsigned)(S.C * 2) + (unsigned)(co * 16) : IDB_OOB;
-                }
+                for (int i = 0; i < NPI; ++i) voff[i] = pix_voff((i * PL + pw) * 8 + q8, S.C, okp[i]);
                 cb = 0;
                 for (int q = 0; q < s; ++q) cb += p.src[q].C;   // first channel of source s inside the normalised concatenation
                 seg = s;
@@ -446,66 +553,20 @@ __global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const Ge
 #pragma unroll
                 for (int i = 0; i < NPI; ++i) raw[i] = __builtin_bit_cast(V8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff[i], soff, 0));
             };
-            auto coeffs = [&]() {                              // k = rstd * gamma, h = beta - mean * k (the first use of the loads above)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float2 st = gst[(ch0 + e) / cpg];
-                    kk[e] = st.y * (e < 4 ? g0v[e] : g1v[e - 4]);
-                    hh[e] = (e < 4 ? b0v[e] : b1v[e - 4]) - st.x * kk[e];
-                }
-            };
+            auto coeffs = [&]() { idb_gn_coeffs(gst, ch0, cpg, rcpg, g0v, g1v, b0v, b1v, kk, hh); };   // the first use of the loads above
             auto put = [&](int i, int buf) {
-                V8 o = raw[i];
-                if (okp[i]) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        float y = to_f32<T>(raw[i][e]) * kk[e] + hh[e];
-                        if (p.gn_in_silu) y = silu_f(y);
-                        o[e] = from_f32<T>(y);
-                    }
-                }
-                *(V8*)(smem + buf * PATCH + ((i * PL + pw) * 8 + q8) * 128 + (lane & 7) * 16) = o;
+                *(V8*)(smem + buf * PATCH + ((i * PL + pw) * 8 + q8) * 128 + (lane & 7) * 16) = idb_gn_norm8<T>(raw[i], okp[i], p.gn_in_silu, kk, hh);
             };
             int s = s0, c = c0, t = t0, buf = 0, done = 0;
-            fetch(s, c);                                       // the first patch is in flight while the statistics are added up
-            {
-                // {mean, rstd} per group of this tile's sample: 8 lanes per group add the pixel-chunk partials in gn_apply_kernel's order
-                // (4 waves x 8 groups = one pass for GroupNorm(32))
-                for (int g0_ = pw * 8; g0_ < G; g0_ += 8 * PL) {
-                    const int g = min(g0_ + (lane >> 3), G - 1), sub = lane & 7;
-                    f32x2 pv[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int ch = min(sub + 8 * u, p.gn_in_chunks - 1);
-                        pv[u] = *(const f32x2*)(p.gn_in_part + (((long long)b0 * p.gn_in_chunks + ch) * G + g) * 2);
-                    }
-                    float a = 0.f, q = 0.f;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        if (sub + 8 * u < p.gn_in_chunks) {
-                            a += pv[u][0];
-                            q += pv[u][1];
-                        }
-                    }
-#pragma unroll
-                    for (int o = 1; o < 8; o <<= 1) {
-                        a += __shfl_xor(a, o, 64);
-                        q += __shfl_xor(q, o, 64);
-                    }
-                    if (g0_ + (lane >> 3) < G && sub == 0) {
-                        const double cnt = (double)p.HW * cpg;
-                        const double mean = (double)a / cnt;
-                        double var = (double)q / cnt - mean * mean;
-                        if (var < 0.0) var = 0.0;
-                        gst[g] = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)p.gn_in_eps)));
-                    }
-                }
-            }
+            setup(s);                                          // the first patch: this wave's first LI units, the MFMA waves fetch the others
+            ch0 = cb + c * 64 + co * 8;
             fetch_gb();
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // barrier S: the statistics are in LDS
+#pragma unroll
+            for (int i = 0; i < LI; ++i) raw[i] = __builtin_bit_cast(V8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff[i], (unsigned)c * 128u, 0));
+            asm volatile("s_barrier" ::: "memory");            // barrier S: MFMA waves 0-3 have put the statistics into LDS
             coeffs();
 #pragma unroll
-            for (int i = 0; i < NPI; ++i) put(i, 0);
+            for (int i = 0; i < LI; ++i) put(i, 0);
             while (done < nk) {
                 const int n = 9 - t < nk - done ? 9 - t : nk - done;
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // first K-step of the chunk: its normalised patch is in LDS
@@ -540,7 +601,6 @@ __global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const Ge
             }
             return;
         }
-        if (wave < 8) asm volatile("s_barrier" ::: "memory");  // barrier S (MFMA waves; the weight loaders pass it behind their first stages)
     }
     if (!GN && wave >= 10) {
         // ---------------- patch loaders ----------------
@@ -691,6 +751,17 @@ __global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const Ge
         }
     };
     V8 af0[MF], wf0[NF], af1[MF], wf1[NF];
+    if constexpr (GN) {
+        // second half of the MFMA waves' prologue: the statistics (waves 0-3), barrier S, this wave's units of the first patch
+        if (wave < 4) idb_gn_part_finish(p, gst, wave, lane, hpv);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // barrier S: the statistics are in LDS
+        float kk[8], hh[8];
+        idb_gn_coeffs(gst, hch0, hcpg, hrcpg, hg0, hg1, hb0, hb1, kk, hh);
+#pragma unroll
+        for (int j = 0; j < NH; ++j)
+            *(V8*)(smem + ((PL * LI + wave * NH + j) * 8 + (lane >> 3)) * 128 + (lane & 7) * 16) = idb_gn_norm8<T>(hraw[j], hok[j], p.gn_in_silu, kk, hh);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // ... are in patch buffer 0 before the barrier that publishes it
+    }
     asm volatile("s_barrier" ::: "memory");
     addr();
 #pragma unroll
