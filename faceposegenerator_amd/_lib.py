@@ -40,6 +40,8 @@ EXPORTS = [
     "idb_verif_cos_scores", "idb_verif_workspace_bytes", "idb_verif_roc",
     "idb_frb_pair_dist", "idb_frb_workspace_bytes", "idb_frb_fold_counts",
     "idb_resize_linear_u8", "idb_fiqa_tail",
+    "idb_diffuse_targets", "idb_objective_workspace_bytes", "idb_objective_mse_x0", "idb_crop_resize_bilinear_f32", "idb_crop_resize_area_f32",
+    "idb_identity_losses",
 ]
 
 
@@ -166,6 +168,12 @@ def load() -> C.CDLL:
         "idb_frb_fold_counts": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, vp, vp, sz, vp]),
         "idb_resize_linear_u8": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "idb_fiqa_tail": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp]),
+        "idb_diffuse_targets": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "idb_objective_workspace_bytes": (sz, [i32, i64]),
+        "idb_objective_mse_x0": (C.c_int, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+        "idb_crop_resize_bilinear_f32": (C.c_int, [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp]),
+        "idb_crop_resize_area_f32": (C.c_int, [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, f32, f32, vp]),
+        "idb_identity_losses": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

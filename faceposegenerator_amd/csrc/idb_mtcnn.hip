@@ -10,9 +10,12 @@
 
 namespace {
 
-// crop + F.interpolate(mode="area") (= adaptive average pooling) + (x - sub) * mul, uint8 NHWC in -> fp32 NCHW out.
-// boxes: [n][5] = {image, y0, y1, x0, x1} (y1 / x1 exclusive, already clipped to the image)
-__global__ __launch_bounds__(256) void crop_resize_area_kernel(const uint8_t* src, int h, int w, int c, const int* boxes, int n, float* out,
+// crop + F.interpolate(mode="area") (= adaptive average pooling) + (x - sub) * mul, uint8 or fp32 NHWC in -> fp32 NCHW out.
+// boxes: [n][5] = {image, y0, y1, x0, x1} (y1 / x1 exclusive, already clipped to the image).  T = float serves a float image in [0, 255]
+// (facenet-pytorch's detect casts a tensor image to float unrounded): the same windows, the same summation order, the same operations, so
+// integer-valued floats give the uint8 instantiation's bits.
+template <typename T>
+__global__ __launch_bounds__(256) void crop_resize_area_kernel(const T* src, int h, int w, int c, const int* boxes, int n, float* out,
                                                                int oh, int ow, float sub, float mul) {
     const long long total = (long long)n * c * oh * ow;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -28,7 +31,7 @@ __global__ __launch_bounds__(256) void crop_resize_area_kernel(const uint8_t* sr
     const int xs = (int)(((long long)ox * iw) / ow), xe = (int)((((long long)(ox + 1)) * iw + ow - 1) / ow);
     float s = 0.f;
     for (int y = ys; y < ye; ++y) {
-        const uint8_t* row = src + (((long long)img * h + (y0 + y)) * w + x0) * c + ch;
+        const T* row = src + (((long long)img * h + (y0 + y)) * w + x0) * c + ch;
         for (int x = xs; x < xe; ++x) s += (float)row[(long long)x * c];
     }
     out[idx] = (s / (float)((ye - ys) * (xe - xs)) - sub) * mul;
@@ -135,19 +138,30 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ 
 
 }  // namespace
 
-extern "C" int idb_crop_resize_area_u8(const uint8_t* src, int32_t batch, int32_t h, int32_t w, int32_t channels, const int32_t* boxes,
-                                       int32_t n, float* out, int32_t out_h, int32_t out_w, float sub, float mul, void* stream) {
-    IDB_REQUIRE(src && boxes && out && batch > 0 && h > 0 && w > 0 && channels > 0 && n >= 0 && out_h > 0 && out_w > 0,
-                "idb_crop_resize_area_u8: bad arguments");
+template <typename T>
+static int crop_resize_area(const char* api, const T* src, int32_t batch, int32_t h, int32_t w, int32_t channels, const int32_t* boxes, int32_t n,
+                            float* out, int32_t out_h, int32_t out_w, float sub, float mul, void* stream) {
+    IDB_REQUIRE(src && boxes && out && batch > 0 && h > 0 && w > 0 && channels > 0 && n >= 0 && out_h > 0 && out_w > 0, "%s: bad arguments", api);
+    IDB_REQUIRE((((uintptr_t)src) & (sizeof(T) - 1)) == 0, "%s: unaligned image", api);
     // the kernel's window count (ye - ys) * (xe - xs) is an int product over a box that lies inside one image; boxes[k * 5] an int index
-    IDB_REQUIRE((long long)h * w < (1LL << 31) && n <= (1 << 28), "idb_crop_resize_area_u8: image plane or box count too large");
+    IDB_REQUIRE((long long)h * w < (1LL << 31) && n <= (1 << 28), "%s: image plane or box count too large", api);
     if (n == 0) return IDB_OK;
     const long long total = (long long)n * channels * out_h * out_w;
-    IDB_REQUIRE(total < (1LL << 31) * 256, "idb_crop_resize_area_u8: too many outputs");
-    hipLaunchKernelGGL(crop_resize_area_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, h, w, channels,
+    IDB_REQUIRE(total < (1LL << 31) * 256, "%s: too many outputs", api);
+    hipLaunchKernelGGL(crop_resize_area_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, h, w, channels,
                        boxes, n, out, out_h, out_w, sub, mul);
-    IDB_CHECK_LAUNCH("idb_crop_resize_area_u8");
+    IDB_CHECK_LAUNCH(api);
     return IDB_OK;
+}
+
+extern "C" int idb_crop_resize_area_u8(const uint8_t* src, int32_t batch, int32_t h, int32_t w, int32_t channels, const int32_t* boxes,
+                                       int32_t n, float* out, int32_t out_h, int32_t out_w, float sub, float mul, void* stream) {
+    return crop_resize_area("idb_crop_resize_area_u8", src, batch, h, w, channels, boxes, n, out, out_h, out_w, sub, mul, stream);
+}
+
+extern "C" int idb_crop_resize_area_f32(const float* src, int32_t batch, int32_t h, int32_t w, int32_t channels, const int32_t* boxes,
+                                        int32_t n, float* out, int32_t out_h, int32_t out_w, float sub, float mul, void* stream) {
+    return crop_resize_area("idb_crop_resize_area_f32", src, batch, h, w, channels, boxes, n, out, out_h, out_w, sub, mul, stream);
 }
 
 extern "C" int idb_conv2d_f32(const float* x, const float* w, const float* bias, const float* prelu, float* y, int32_t batch, int32_t cin,

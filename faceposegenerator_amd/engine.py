@@ -1060,9 +1060,10 @@ class HipEngine:
         self.last_forward_launches = int(self.lib.idb_launch_count() - launches0)     # kernels of ONE (CFG) UNet forward
         return eps
 
-    def unet_forward(self, sample: torch.Tensor, timestep, encoder_hidden_states: torch.Tensor) -> torch.Tensor:
+    def unet_forward(self, sample: torch.Tensor, timestep, encoder_hidden_states: torch.Tensor, nhwc: bool = False) -> torch.Tensor:
         """API form (train_ID-Booth.py:1040-1046): sample [B,4,h,w], timestep scalar or [B],
-        encoder_hidden_states [B,L,cross_dim]; returns eps NCHW fp32."""
+        encoder_hidden_states [B,L,cross_dim]; returns eps NCHW fp32.  With nhwc the conv_out GEMM's own [B*h*w, C] output is
+        returned untransposed: an arena tensor, valid until the next engine call (idb_objective_mse_x0 reads it in that layout)."""
         self.arena.reset()
         self._pinned.clear()
         B, _, h, w_ = sample.shape
@@ -1075,6 +1076,8 @@ class HipEngine:
         self._rep = 1                                  # API form: LoRA groups (if any) partition the GIVEN batch contiguously
         kv = self.cross_kv(ctx, B, n_ctx)
         eps = self.unet_nhwc(lat, 1, (tp, 0, self.tproj_total), kv, n_ctx)
+        if nhwc:
+            return eps
         out = torch.empty((B, self.ucfg.out_channels, h, w_), dtype=torch.float32, device=self.device)
         L.check(self.lib.idb_f32_nhwc_to_nchw(eps.data_ptr(), out.data_ptr(), B, h * w_, self.ucfg.out_channels, _stream()),
                 "idb_f32_nhwc_to_nchw")

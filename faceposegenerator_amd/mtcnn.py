@@ -12,7 +12,7 @@ scale and 0.7 across scales, regression + squaring, R-Net on 24x24 and O-Net on 
 0.6 / 0.7 / 0.7, final "Min"-overlap NMS — PARITY UNPINNED against upstream; the HIP path is checked against
 oracle/mtcnn_oracle.py (plain torch CPU ops) with seeded synthetic weights.
 
-Every network layer is a HIP kernel of libidb_kernels.so (idb_crop_resize_area_u8, idb_conv2d_f32, idb_maxpool2d_f32,
+Every network layer is a HIP kernel of libidb_kernels.so (idb_crop_resize_area_u8 / _f32, idb_conv2d_f32, idb_maxpool2d_f32,
 idb_softmax_pairs_f32; fp32, csrc/idb_mtcnn.hip); the data-dependent control logic between the stages works on a few hundred
 boxes and runs on the host, as in upstream."""
 from __future__ import annotations
@@ -208,14 +208,14 @@ class MTCNN:
         L.check(self.lib.idb_softmax_pairs_f32(logits.data_ptr(), p.data_ptr(), b, hw, self._st()), "idb_softmax_pairs_f32")
         return p
 
-    def _resample(self, imgs_u8, boxes_np, oh, ow):
-        """boxes_np int32 [n][5] = image, y0, y1, x0, x1 -> normalised fp32 [n][3][oh][ow]"""
+    def _resample(self, imgs, boxes_np, oh, ow):
+        """imgs uint8 or float32 NHWC; boxes_np int32 [n][5] = image, y0, y1, x0, x1 -> normalised fp32 [n][3][oh][ow]"""
         n = boxes_np.shape[0]
         bx = torch.from_numpy(np.ascontiguousarray(boxes_np, dtype=np.int32)).to(self.device)
         out = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=self.device)
-        b, h, w_, c = imgs_u8.shape
-        L.check(self.lib.idb_crop_resize_area_u8(imgs_u8.data_ptr(), b, h, w_, c, bx.data_ptr(), n, out.data_ptr(), oh, ow, 127.5, 0.0078125,
-                                                 self._st()), "idb_crop_resize_area_u8")
+        b, h, w_, c = imgs.shape
+        name = "idb_crop_resize_area_u8" if imgs.dtype == torch.uint8 else "idb_crop_resize_area_f32"
+        L.check(getattr(self.lib, name)(imgs.data_ptr(), b, h, w_, c, bx.data_ptr(), n, out.data_ptr(), oh, ow, 127.5, 0.0078125, self._st()), name)
         return out
 
     def pnet(self, x):
@@ -274,7 +274,10 @@ class MTCNN:
         return kept[np.argsort(-scores[kept], kind="stable")]
 
     def detect_faces(self, imgs: torch.Tensor):
-        """imgs uint8 [B,H,W,3] on the device -> (boxes [n,5] float32 incl. score, image index [n], points [n,5,2]) as numpy."""
+        """imgs uint8 or float32 (values in [0, 255], used unrounded) [B,H,W,3], contiguous on the device -> (boxes [n,5] float32 incl.
+        score, image index [n], points [n,5,2]) as numpy."""
+        if imgs.dtype not in (torch.uint8, torch.float32):
+            raise ValueError("expected a uint8 or float32 image batch [B, H, W, 3]")
         B, h, w_, _ = imgs.shape
         thr = self.thresholds
         full = np.array([[b, 0, h, 0, w_] for b in range(B)], dtype=np.int32)
@@ -337,13 +340,15 @@ class MTCNN:
 
     def detect(self, img, landmarks: bool = False):
         """``mtcnn.detect(img_batch, landmarks=True)`` (detect_align_crop_data.py:99): uint8 NHWC batch (tensor or array) ->
-        per-image object arrays of boxes [n,4], probabilities [n] and landmarks [n,5,2]; None where no face was found."""
+        per-image object arrays of boxes [n,4], probabilities [n] and landmarks [n,5,2]; None where no face was found.
+        A float32 batch in [0, 255] is taken as it is, unrounded, as upstream's ``.float()`` does with the ``image * 255`` tensor of
+        latents_to_image_for_mtcnn (train_ID-Booth.py:433-442, :1085); uint8 input takes the u8 kernel."""
         t = torch.as_tensor(np.asarray(img) if not torch.is_tensor(img) else img)
         single = t.ndim == 3
         if single:
             t = t[None]
-        if t.dtype != torch.uint8 or t.ndim != 4 or t.shape[-1] != 3:
-            raise ValueError("expected a uint8 image batch [B, H, W, 3]")
+        if t.dtype not in (torch.uint8, torch.float32) or t.ndim != 4 or t.shape[-1] != 3:
+            raise ValueError("expected a uint8 or float32 image batch [B, H, W, 3]")
         t = t.to(self.device).contiguous()
         boxes, inds, pts = self.detect_faces(t)
         out_b, out_p, out_l = [], [], []

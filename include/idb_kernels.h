@@ -617,6 +617,60 @@ int idb_fiqa_tail(const float* emb, const float* weight, const float* bias, int3
 int idb_vae_sample(const float* moments, const float* noise, float scale, float* latents, float* mean_out,
                    float* logvar_out, int32_t batch, int32_t channels, int32_t hw, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The training objective's forward pass (train_ID-Booth.py:996-1134, evaluated under no_grad: a checkpoint's validation losses) — the
+ * kernels between vae.encode, the UNet, vae.decode, MTCNN.detect and ArcFace.  fp32 in and out, asynchronous on `stream`, no
+ * synchronisation; every entry validates its arguments before any HIP call (IDB_EINVAL, or IDB_EUNSUPPORTED for a prediction type or
+ * an embedding width the kernels do not implement).  Sums are accumulated in double in a fixed order without floating-point atomics:
+ * bit-identical from run to run.
+ *   Schedule arguments (idb_diffuse_targets, idb_objective_mse_x0): timesteps int32 [batch] and alphas_cumprod fp32 [n_train], both in
+ *       device memory; sample b uses a = alphas_cumprod[t_b], sqrt(a) and sqrt(1 - a) taken in double.  A timestep outside
+ *       [0, n_train) cannot be refused without a synchronisation: it is CLAMPED into the table.  prediction_type 0 = epsilon,
+ *       1 = v_prediction.  1 <= batch <= 65535, channels * hw < 2^31.
+ *   idb_diffuse_targets: replaces `noise_scheduler.add_noise(model_input, noise, timesteps)` (:1018) and the target selection
+ *       (:1055-1058: `noise`, or `noise_scheduler.get_velocity(model_input, noise, timesteps)`) in one launch.  x0, noise, noisy, target:
+ *       NCHW [batch][channels][hw].  noisy = sqrt(a) x0 + sqrt(1 - a) noise; target = noise, or sqrt(a) noise - sqrt(1 - a) x0; each
+ *       evaluated in double and rounded to fp32 once.  target may be NULL.  16-byte accesses when channels * hw % 4 == 0 and every
+ *       tensor is 16-byte aligned.
+ *   idb_objective_mse_x0: replaces `F.mse_loss(model_pred.float(), target.float())` per sample (:1072-1074; sse[b] is the SUM of squared
+ *       differences as double, the caller divides by the element count and averages the samples of a chunk) and
+ *       `noise_scheduler.step(model_pred, t, noisy).pred_original_sample` (:1081, :1109), in one pass.  pred: NCHW, or with pred_nhwc the
+ *       [batch][hw][channels] layout idb_gemm writes the UNet's output in; target, noisy, x0_pred: NCHW.  x0_pred (optional; needs noisy):
+ *       epsilon (noisy - sqrt(1 - a) pred) / sqrt(a), v_prediction sqrt(a) noisy - sqrt(1 - a) pred, no clipping (SD-2.1's scheduler has
+ *       clip_sample = false), evaluated in double and rounded once.  Per-workgroup partial sums go to ws (8-byte aligned, at least
+ *       idb_objective_workspace_bytes), then one workgroup per sample adds them in ascending order; the order does not depend on pred's
+ *       layout.  Two launches.
+ *   idb_objective_workspace_bytes(batch, channels * hw): enough for any split of that product into channels and hw; 0 for arguments
+ *       idb_objective_mse_x0 would refuse.
+ *   idb_crop_resize_bilinear_f32: replaces the bounding-box crop `img[y0:y1, x0:x1]` (:1090, :1124) and cropped_image_to_arcface_input
+ *       (:445-455: permute, torchvision `resize(img, (112, 112), antialias=None)`, `((img / 255) - 0.5) / 0.5`).  src: float NHWC
+ *       [batch][h][w][channels] in [0, 255]; boxes as for idb_crop_resize_area_u8; out fp32 NCHW [n][channels][out_h][out_w].  The resize
+ *       is F.interpolate(mode="bilinear", align_corners=False, antialias=False) restated from ATen (PARITY UNPINNED against a torchvision
+ *       binary): half-pixel centres, the source coordinate clamped at 0, second tap min(i + 1, size - 1), no antialiasing when
+ *       shrinking.  Coordinates and weights are computed in double and rounded to fp32 once; the taps are combined in fp32.
+ *   idb_crop_resize_area_f32: idb_crop_resize_area_u8 for a float image (facenet-pytorch's detect casts a tensor image to float
+ *       unrounded; the reference hands it `image * 255` as floats, latents_to_image_for_mtcnn :433-442): same boxes, sub, mul, limits
+ *       and summation order; on integer-valued floats in [0, 255] the output equals the u8 entry's bit for bit.
+ *   idb_identity_losses: replaces `cos(pred_arcface_features, gt_arcface_embed[0])` with nn.CosineSimilarity(dim=1, eps=1e-6) (:972,
+ *       :1096), `1 - arcface_cos_similarity` (:1098) and, with neg, TripletMarginWithDistanceLoss(distance_function=cosine_distance)
+ *       at its default margin 1 (:974-979, :1133; F.cosine_similarity's eps 1e-8).  feat, pos, neg: fp32 [n][d]; cos, identity,
+ *       triplet: fp32 [n]; neg and triplet are both given or both NULL.  cos_eps(a, b) = a.b / (max(|a|, eps) max(|b|, eps)) (torch
+ *       clamps each norm); identity = 1 - cos_1e-6(feat, pos); triplet = max((1 - cos_1e-8(feat, pos)) - (1 - cos_1e-8(feat, neg)) + 1, 0).
+ *       Dot products and norms in double, one rounding per output.  1 <= d <= 8192.
+ * ------------------------------------------------------------------------------------------ */
+int idb_diffuse_targets(const float* x0, const float* noise, const int32_t* timesteps, const float* alphas_cumprod, int32_t n_train,
+                        int32_t prediction_type, int32_t batch, int32_t channels, int32_t hw, float* noisy, float* target, void* stream);
+size_t idb_objective_workspace_bytes(int32_t batch, int64_t chw);
+int idb_objective_mse_x0(const float* pred, int32_t pred_nhwc, const float* target, const float* noisy, const int32_t* timesteps,
+                         const float* alphas_cumprod, int32_t n_train, int32_t prediction_type, int32_t batch, int32_t channels, int32_t hw,
+                         double* sse, float* x0_pred, void* ws, size_t ws_bytes, void* stream);
+int idb_crop_resize_bilinear_f32(const float* src, int32_t batch, int32_t h, int32_t w, int32_t channels, const int32_t* boxes, int32_t n,
+                                 float* out, int32_t out_h, int32_t out_w, void* stream);
+int idb_crop_resize_area_f32(const float* src, int32_t batch, int32_t h, int32_t w, int32_t channels, const int32_t* boxes, int32_t n,
+                             float* out, int32_t out_h, int32_t out_w, float sub, float mul, void* stream);
+int idb_identity_losses(const float* feat, const float* pos, const float* neg, int32_t n, int32_t d, float* cos, float* identity,
+                        float* triplet, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
