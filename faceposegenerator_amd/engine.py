@@ -195,6 +195,12 @@ class HipEngine:
                 "idb_pack_matrix")
         return dst
 
+    def _pack_conv_bias(self, sd: SD, src: str, dst: Optional[str] = None) -> None:
+        """Conv2d `src` of the state dict -> ``w[dst.w]`` ([Cout][tap][Cin] operand dtype) and ``w[dst.b]`` (fp32); dst defaults to src."""
+        dst = dst or src
+        self.w[dst + ".w"] = self._pack_conv(sd[src + ".weight"])
+        self.w[dst + ".b"] = self._f32(sd[src + ".bias"])
+
     def _empty_tiled(self, n: int, k: int) -> torch.Tensor:
         t = torch.empty((self.lib.idb_tiled_weight_bytes(n, k) // 2,), dtype=self.tdt, device=self.device)
         t._tiled = (n, k)
@@ -216,8 +222,7 @@ class HipEngine:
         captured graph)."""
         n, k = w.shape
         if out is None:
-            out = torch.empty((self.lib.idb_tiled_weight_bytes(n, k) // 2,), dtype=self.tdt, device=self.device)
-            out._tiled = (n, k)
+            out = self._empty_tiled(n, k)
         L.check(self.lib.idb_tile_weight(w.data_ptr(), out.data_ptr(), n, k, self.dt, _stream()), "idb_tile_weight")
         return out
 
@@ -232,9 +237,9 @@ class HipEngine:
         for i in ("1", "2"):
             w[f"{name}.gn{i}.g"] = self._f32(sd[f"{name}.norm{i}.weight"])
             w[f"{name}.gn{i}.b"] = self._f32(sd[f"{name}.norm{i}.bias"])
-        w[f"{name}.conv1.w"] = self._pack_conv(sd[f"{name}.conv1.weight"])
-        w[f"{name}.conv1.b"] = self._f32(sd[f"{name}.conv1.bias"])
-        if split_at:                                    # up-path resnet: norm1 + conv1 over cat[x, skip] as TWO 3x3 sources (fused GroupNorm)
+        self._pack_conv_bias(sd, f"{name}.conv1")
+        # up-path resnet: norm1 + conv1 over cat[x, skip] as TWO 3x3 sources; read only by the fused GroupNorm of the resnet convs
+        if split_at and self._gn_conv and self._gn_conv_resnet:
             w1 = sd[f"{name}.conv1.weight"]
             w[f"{name}.conv1.wsplit"] = torch.cat([self._pack_conv(w1[:, :split_at].contiguous()), self._pack_conv(w1[:, split_at:].contiguous())],
                                                   dim=1).contiguous()
@@ -269,16 +274,14 @@ class HipEngine:
             resnets += blk["resnets"]
             attns += blk["attns"]
             if blk["down"]:
-                w[blk["down"] + ".w"] = self._pack_conv(sd[blk["down"] + ".weight"])
-                w[blk["down"] + ".b"] = self._f32(sd[blk["down"] + ".bias"])
+                self._pack_conv_bias(sd, blk["down"])
         resnets += g.mid["resnets"]
         attns.append(g.mid["attn"])
         for blk in g.up:
             resnets += blk["resnets"]
             attns += blk["attns"]
             if blk["up"]:
-                w[blk["up"] + ".w"] = self._pack_conv(sd[blk["up"] + ".weight"])
-                w[blk["up"] + ".b"] = self._f32(sd[blk["up"] + ".bias"])
+                self._pack_conv_bias(sd, blk["up"])
         tw, tb, off = [], [], 0
         for r in resnets:
             self._pack_resnet(sd, r.name, True, split_at=(r.cin - r.skip_channels) if getattr(r, "skip_channels", 0) else 0)
@@ -333,25 +336,21 @@ class HipEngine:
             w[f"{n}.ff2.b"] = self._f32(sd[f"{b}.ff.net.2.bias"])
         w["conv_norm_out.g"] = self._f32(sd["conv_norm_out.weight"])
         w["conv_norm_out.b"] = self._f32(sd["conv_norm_out.bias"])
-        w["conv_out.w"] = self._pack_conv(sd["conv_out.weight"])
-        w["conv_out.b"] = self._f32(sd["conv_out.bias"])
+        self._pack_conv_bias(sd, "conv_out")
         self._attn_specs = attns
         self._resnet_specs = resnets
         self._tile_static_weights()
         self.set_lora(None)
 
-    def _attn_dst(self, a: S.AttnSpec, attn: str, t: str) -> Tuple[torch.Tensor, int]:
-        """(packed matrix, row offset) that holds projection `t` of `attn`."""
+    def _lora_dst(self, a: S.AttnSpec, attn: str, t: str):
+        """(packed [n][K] matrix, row offset, fold) of projection `t` of `attn`.  fold = (folded matrix, u, v, LayerNorm gamma, beta) for
+        the projections that read a LayerNorm output — attn1 to_q/k/v (norm1), attn2 to_q (norm2) — at the same row offset; else None."""
         n, c = a.name, a.channels
-        if attn == "attn1":
-            if t == "to_out.0":
-                return self.w_rows[f"{n}.o1.w"], 0
-            return self.w_rows[f"{n}.qkv.w"], {"to_q": 0, "to_k": c, "to_v": 2 * c}[t]
-        if t == "to_q":
-            return self.w_rows[f"{n}.q2.w"], 0
-        if t == "to_out.0":
-            return self.w_rows[f"{n}.o2.w"], 0
-        return self.w_rows[f"{n}.kv2.w"], {"to_k": 0, "to_v": c}[t]
+        mat, row0, ln = {("attn1", "to_q"): ("qkv", 0, "ln1"), ("attn1", "to_k"): ("qkv", c, "ln1"), ("attn1", "to_v"): ("qkv", 2 * c, "ln1"),
+                         ("attn1", "to_out.0"): ("o1", 0, None), ("attn2", "to_q"): ("q2", 0, "ln2"), ("attn2", "to_k"): ("kv2", 0, None),
+                         ("attn2", "to_v"): ("kv2", c, None), ("attn2", "to_out.0"): ("o2", 0, None)}[attn, t]
+        fold = ln and (self.w_rows[f"{n}.{mat}.wln"], self.w[f"{n}.{mat}.u"], self.w[f"{n}.{mat}.v"], self.w[f"{n}.{ln}.g"], self.w[f"{n}.{ln}.b"])
+        return self.w_rows[f"{n}.{mat}.w"], row0, fold
 
     def set_lora(self, lora: Optional[SD], scale: float = 1.0, alphas: Optional[Dict[str, float]] = None) -> None:
         """(Re)build the 128 LoRA-affected matrices: W' = W + scale*(alpha/r) * B A in fp32, then one
@@ -363,51 +362,37 @@ class HipEngine:
             for attn in ("attn1", "attn2"):
                 for t in S.LORA_TARGETS:
                     key = f"{b}.{attn}.{t}"
-                    mat, row0 = self._attn_dst(a, attn, t)
+                    mat, row0, fold = self._lora_dst(a, attn, t)
                     master = self.master[key]
                     rows, cols = master.shape
                     dst_ptr = mat.data_ptr() + row0 * mat.shape[1] * 2
                     assert mat.shape[1] == cols
                     la = None if lora is None else lora.get(key + ".lora_A.weight")
-                    # folded-LayerNorm copy of the projections that read a LayerNorm output: attn1 to_q/k/v (norm1), attn2 to_q (norm2)
-                    fold = None
-                    if attn == "attn1" and t != "to_out.0":
-                        fold = (self.w_rows[f"{a.name}.qkv.wln"], self.w[f"{a.name}.qkv.v"], row0, self.w[f"{a.name}.ln1.g"], self.w[f"{a.name}.ln1.b"],
-                                self.w[f"{a.name}.qkv.u"])
-                    elif attn == "attn2" and t == "to_q":
-                        fold = (self.w_rows[f"{a.name}.q2.wln"], self.w[f"{a.name}.q2.v"], 0, self.w[f"{a.name}.ln2.g"], self.w[f"{a.name}.ln2.b"],
-                                self.w[f"{a.name}.q2.u"])
+                    la_d, lb_d, rank, sc = None, None, 0, 0.0          # no adapter for this projection
                     if la is None:
                         L.check(self.lib.idb_pack_matrix(master.data_ptr(), dst_ptr, rows, cols, 0, self.dt, _stream()),
                                 "idb_pack_matrix")
-                        if fold is not None:
-                            fmat, fv, fr0, gam, bet, fu = fold
-                            L.check(self.lib.idb_lora_merge_scaled(master.data_ptr(), None, None, fmat.data_ptr() + fr0 * cols * 2, rows, cols, 0, 0.0,
-                                                                   gam.data_ptr(), self.dt, _stream()), "idb_lora_merge_scaled")
-                            L.check(self.lib.idb_ln_fold_vectors(master.data_ptr(), None, None, 0, 0.0, fmat.data_ptr() + fr0 * cols * 2, bet.data_ptr(),
-                                                                 None, fu.data_ptr() + 4 * fr0, fv.data_ptr() + 4 * fr0, rows, cols, 0, self.dt,
-                                                                 _stream()), "idb_ln_fold_vectors")
-                        continue
-                    lb = lora[key + ".lora_B.weight"]
-                    rank = la.shape[0]
-                    if tuple(la.shape) != (rank, cols) or tuple(lb.shape) != (rows, rank):
-                        raise ValueError(f"LoRA shapes for {key}: A {tuple(la.shape)} B {tuple(lb.shape)} do not match "
-                                         f"W {rows}x{cols}")
-                    alpha = (alphas or {}).get(key, float(rank))
-                    la_d, lb_d = self._f32(la), self._f32(lb)
-                    L.check(self.lib.idb_lora_merge(master.data_ptr(), la_d.data_ptr(), lb_d.data_ptr(), dst_ptr, rows, cols,
-                                                    rank, float(scale * alpha / rank), self.dt, _stream()), "idb_lora_merge")
-                    if fold is not None:
-                        # u = row sums of the rounded folded operand (what the MFMA multiplies), v = (W + s B A) beta: written IN PLACE
-                        # (captured graphs hold these addresses)
-                        fmat, fv, fr0, gam, bet, fu = fold
-                        sc = float(scale * alpha / rank)
-                        L.check(self.lib.idb_lora_merge_scaled(master.data_ptr(), la_d.data_ptr(), lb_d.data_ptr(), fmat.data_ptr() + fr0 * cols * 2,
-                                                               rows, cols, rank, sc, gam.data_ptr(), self.dt, _stream()), "idb_lora_merge_scaled")
-                        L.check(self.lib.idb_ln_fold_vectors(master.data_ptr(), la_d.data_ptr(), lb_d.data_ptr(), rank, sc, fmat.data_ptr() + fr0 * cols * 2,
-                                                             bet.data_ptr(), None, fu.data_ptr() + 4 * fr0, fv.data_ptr() + 4 * fr0, rows, cols, 0,
-                                                             self.dt, _stream()), "idb_ln_fold_vectors")
-                    used += 1
+                    else:
+                        lb = lora[key + ".lora_B.weight"]
+                        rank = la.shape[0]
+                        if tuple(la.shape) != (rank, cols) or tuple(lb.shape) != (rows, rank):
+                            raise ValueError(f"LoRA shapes for {key}: A {tuple(la.shape)} B {tuple(lb.shape)} do not match "
+                                             f"W {rows}x{cols}")
+                        alpha = (alphas or {}).get(key, float(rank))
+                        la_d, lb_d, sc = self._f32(la), self._f32(lb), float(scale * alpha / rank)
+                        L.check(self.lib.idb_lora_merge(master.data_ptr(), la_d.data_ptr(), lb_d.data_ptr(), dst_ptr, rows, cols,
+                                                        rank, sc, self.dt, _stream()), "idb_lora_merge")
+                        used += 1
+                    if fold:
+                        # folded-LayerNorm copy: u = row sums of the rounded folded operand (what the MFMA multiplies), v = (W + s B A) beta:
+                        # written IN PLACE (captured graphs hold these addresses)
+                        fmat, fu, fv, gam, bet = fold
+                        fdst = fmat.data_ptr() + row0 * cols * 2
+                        L.check(self.lib.idb_lora_merge_scaled(master.data_ptr(), _ptr(la_d), _ptr(lb_d), fdst, rows, cols, rank, sc,
+                                                               gam.data_ptr(), self.dt, _stream()), "idb_lora_merge_scaled")
+                        L.check(self.lib.idb_ln_fold_vectors(master.data_ptr(), _ptr(la_d), _ptr(lb_d), rank, sc, fdst, bet.data_ptr(), None,
+                                                             fu.data_ptr() + 4 * row0, fv.data_ptr() + 4 * row0, rows, cols, 0, self.dt,
+                                                             _stream()), "idb_ln_fold_vectors")
         if self._w_tiled:                                # the forward reads the tiled copies: refill them IN PLACE (captured graphs)
             for key, rows_t in self.w_rows.items():
                 self.tile_weight(rows_t, out=self.w[key])
@@ -456,30 +441,33 @@ class HipEngine:
         """LoRA-affected operand `key`: the grouped buffer while set_lora_groups is active, else the single merged one."""
         return self.wg[key] if self.groups > 1 else self.w[key]
 
+    def _pack_vae_mid(self, sd: SD, side: str) -> None:
+        """`side`.mid_block (side: "decoder" / "encoder"): two resnets around one single-head attention."""
+        w = self.w
+        for nm in (f"{side}.mid_block.resnets.0", f"{side}.mid_block.resnets.1"):
+            self._pack_resnet(sd, nm, False)
+        a = f"{side}.mid_block.attentions.0"
+        w[f"{a}.gn.g"] = self._f32(sd[f"{a}.group_norm.weight"])
+        w[f"{a}.gn.b"] = self._f32(sd[f"{a}.group_norm.bias"])
+        for t, short in (("to_q", "q"), ("to_k", "k"), ("to_v", "v"), ("to_out.0", "o")):
+            w[f"{a}.{short}.w"] = self._pack_mat(sd[f"{a}.{t}.weight"])
+            w[f"{a}.{short}.b"] = self._f32(sd[f"{a}.{t}.bias"])
+
     def _pack_vae(self, sd: SD) -> None:
         w, g = self.w, self.vgraph
         w["v.pq.w"] = self._f32(sd["post_quant_conv.weight"].reshape(self.vcfg.latent_channels, -1))
         w["v.pq.b"] = self._f32(sd["post_quant_conv.bias"])
         w["v.conv_in.w"] = self._f32(sd["decoder.conv_in.weight"])
         w["v.conv_in.b"] = self._f32(sd["decoder.conv_in.bias"])
-        for nm in ("decoder.mid_block.resnets.0", "decoder.mid_block.resnets.1"):
-            self._pack_resnet(sd, nm, False)
-        a = "decoder.mid_block.attentions.0"
-        w[f"{a}.gn.g"] = self._f32(sd[f"{a}.group_norm.weight"])
-        w[f"{a}.gn.b"] = self._f32(sd[f"{a}.group_norm.bias"])
-        for t, short in (("to_q", "q"), ("to_k", "k"), ("to_v", "v"), ("to_out.0", "o")):
-            w[f"{a}.{short}.w"] = self._pack_mat(sd[f"{a}.{t}.weight"])
-            w[f"{a}.{short}.b"] = self._f32(sd[f"{a}.{t}.bias"])
+        self._pack_vae_mid(sd, "decoder")
         for blk in g.up:
             for name, _, _ in blk["resnets"]:
                 self._pack_resnet(sd, name, False)
             if blk["up"]:
-                w[blk["up"] + ".w"] = self._pack_conv(sd[blk["up"] + ".weight"])
-                w[blk["up"] + ".b"] = self._f32(sd[blk["up"] + ".bias"])
+                self._pack_conv_bias(sd, blk["up"])
         w["v.norm_out.g"] = self._f32(sd["decoder.conv_norm_out.weight"])
         w["v.norm_out.b"] = self._f32(sd["decoder.conv_norm_out.bias"])
-        w["v.conv_out.w"] = self._pack_conv(sd["decoder.conv_out.weight"])
-        w["v.conv_out.b"] = self._f32(sd["decoder.conv_out.bias"])
+        self._pack_conv_bias(sd, "decoder.conv_out", "v.conv_out")
         self._tile_static_weights()
 
     def pack_vae_encoder(self, sd: SD) -> None:
@@ -493,16 +481,8 @@ class HipEngine:
             for name, _, _ in blk["resnets"]:
                 self._pack_resnet(sd, name, False)
             if blk["down"]:
-                w[blk["down"] + ".w"] = self._pack_conv(sd[blk["down"] + ".weight"])
-                w[blk["down"] + ".b"] = self._f32(sd[blk["down"] + ".bias"])
-        for nm in ("encoder.mid_block.resnets.0", "encoder.mid_block.resnets.1"):
-            self._pack_resnet(sd, nm, False)
-        a = "encoder.mid_block.attentions.0"
-        w[f"{a}.gn.g"] = self._f32(sd[f"{a}.group_norm.weight"])
-        w[f"{a}.gn.b"] = self._f32(sd[f"{a}.group_norm.bias"])
-        for t, short in (("to_q", "q"), ("to_k", "k"), ("to_v", "v"), ("to_out.0", "o")):
-            w[f"{a}.{short}.w"] = self._pack_mat(sd[f"{a}.{t}.weight"])
-            w[f"{a}.{short}.b"] = self._f32(sd[f"{a}.{t}.bias"])
+                self._pack_conv_bias(sd, blk["down"])
+        self._pack_vae_mid(sd, "encoder")
         w["ve.norm_out.g"] = self._f32(sd["encoder.conv_norm_out.weight"])
         w["ve.norm_out.b"] = self._f32(sd["encoder.conv_norm_out.bias"])
         wq = sd["quant_conv.weight"].double().reshape(2 * cfg.latent_channels, 2 * cfg.latent_channels)
@@ -518,13 +498,27 @@ class HipEngine:
     # ------------------------------------------------------------------------------------
     # kernel wrappers
     # ------------------------------------------------------------------------------------
-    def _workspace(self, nbytes: int) -> torch.Tensor:
-        if nbytes > self._ws.numel():
+    def _grown(self, attr: str, nbytes: int, factor: float, what: str) -> torch.Tensor:
+        """The uint8 workspace ``self.<attr>`` with at least nbytes.  An outgrown one is retired, not freed: captured graphs hold
+        its address and keep writing there, so it stays alive and private to them; under capture nothing may grow."""
+        ws = getattr(self, attr)
+        if nbytes > ws.numel():
             if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("split-K workspace would grow during graph capture; run one eager warm-up first")
-            self._retired.append(self._ws)      # captured graphs hold the old address: keep it alive (and private to them)
-            self._ws = torch.empty(int(nbytes * 1.25), dtype=torch.uint8, device=self.device)
-        return self._ws
+                raise RuntimeError(f"{what} workspace would grow during graph capture; run one eager warm-up first")
+            self._retired.append(ws)
+            ws = torch.empty(int(nbytes * factor), dtype=torch.uint8, device=self.device)
+            setattr(self, attr, ws)
+        return ws
+
+    def _workspace(self, nbytes: int) -> torch.Tensor:
+        return self._grown("_ws", nbytes, 1.25, "split-K")
+
+    def _desc(self, srcs, w: torch.Tensor, n: int, batch: int, oh: int, ow: int, geglu=False, w_ptr: Optional[int] = None, **fields):
+        """idb_gemm_desc with the fields a launch and the plan probes derive the same way: w_layout from w's ``_tiled`` tag, geglu and
+        the output row length that follows from it (a launch into a wider buffer overrides out_ld).  srcs hold addresses."""
+        fields.setdefault("out_ld", n // 2 if geglu else n)
+        return L.gemm_desc(self.dt, srcs, w.data_ptr() if w_ptr is None else w_ptr, n, batch, oh, ow, geglu=int(geglu),
+                           w_layout=1 if getattr(w, "_tiled", None) is not None else 0, **fields)
 
     def gemm(self, srcs, w: torch.Tensor, n: int, batch: int, oh: int, ow: int, bias=None, sbias=None,
              residual=None, geglu=False, stride=1, out_f32=False, out_scale=0.0, split_k=0, tile=0,
@@ -534,13 +528,12 @@ class HipEngine:
         row_stats: also emit the per-row partial sums a folded LayerNorm of the output needs (``out._rs = (buffer, tiles)``) when the
         plan can; ln = (stats, tiles, u, v, eps): A holds raw rows, w the gamma-scaled weights (idb_gemm_desc.ln_*)."""
         m = batch * oh * ow
-        ncols = n // 2 if geglu else n
         own_out = out is None
         if out is None:
-            out = self.arena.alloc((m, ncols), torch.float32 if out_f32 else self.tdt)
-        f = dict(stride=stride, bias=_ptr(bias), residual=_ptr(residual), geglu=int(geglu), out=out.data_ptr(),
-                 out_dtype=L.IDB_F32 if out_f32 else self.dt, out_ld=out.shape[-1], split_k=split_k, tile=tile, out_scale=out_scale, flags=flags,
-                 act=act, pad_mode=pad_mode, w_layout=1 if getattr(w, "_tiled", None) is not None else 0,
+            out = self.arena.alloc((m, n // 2 if geglu else n), torch.float32 if out_f32 else self.tdt)
+        # ---- 1. the descriptor
+        f = dict(stride=stride, bias=_ptr(bias), residual=_ptr(residual), out=out.data_ptr(), out_dtype=L.IDB_F32 if out_f32 else self.dt,
+                 out_ld=out.shape[-1], split_k=split_k, tile=tile, out_scale=out_scale, flags=flags, act=act, pad_mode=pad_mode,
                  counters=self._counters.data_ptr(), counters_len=self._counters.numel())
         if sbias is not None:
             f.update(sample_bias=sbias[0].data_ptr() + 4 * sbias[1], sample_bias_ld=sbias[2])
@@ -552,25 +545,26 @@ class HipEngine:
             rep = self._rep
             if m % (rep * G):
                 raise ValueError(f"grouped weights: {m} rows do not divide into {rep} x {G} groups")
-            # where the library will refuse this launch (run group by group below), its two queries answer 0: no row statistics out,
-            # no folded LayerNorm in
+            # where the library will refuse this launch (run group by group in _launch), its two queries answer 0: no row statistics
+            # out, no folded LayerNorm in
             f.update(w_groups=G, w_group_rows=m // (rep * G), w_group_stride=w.shape[1] * 2)
-        d = L.gemm_desc(self.dt, [(t.data_ptr(), *rest) for t, *rest in srcs], w.data_ptr(), n, batch, oh, ow, **f)
-        rs_buf = None
+        d = self._desc([(t.data_ptr(), *rest) for t, *rest in srcs], w, n, batch, oh, ow, geglu, **f)
+        # ---- 2. the optional outputs and inputs the plan can carry: row statistics, a folded LayerNorm, GroupNorm partials
+        rs = None
         if row_stats and self._ln_fold:
             nt = self.lib.idb_gemm_row_stats_tiles(C.byref(d))
             if nt > 0:
-                rs_buf = self.arena.alloc((m * nt * 2,), torch.float32)
-                d.row_stats_out = rs_buf.data_ptr()
+                rs = (self.arena.alloc((m * nt * 2,), torch.float32), nt)
+                d.row_stats_out = rs[0].data_ptr()
         if ln is not None:
             if self.lib.idb_gemm_folds_layernorm(C.byref(d)) == 0:      # this plan cannot fold (split-K): caller keeps idb_layernorm
                 if own_out:
                     self.arena.free(out)
-                if rs_buf is not None:
-                    self.arena.free(rs_buf)
+                if rs is not None:
+                    self.arena.free(rs[0])
                 return None
             d.ln_stats, d.ln_tiles, d.ln_u, d.ln_v, d.ln_eps = ln[0].data_ptr(), ln[1], ln[2].data_ptr(), ln[3].data_ptr(), ln[4]
-        gn_part = None
+        gn = None
         if gn_stats and self._gn_fuse and (oh * ow) % 64 == 0 and oh * ow <= 4096 and not geglu and not out_f32 and n % gn_stats == 0:
             # the GroupNorm that consumes `out` next gets its first pass from this GEMM: from its split-K reduce launch, or — without a
             # split — from its own LDS-staged epilogue when the column tiles hold whole groups (idb_kernels.h); otherwise the library
@@ -579,48 +573,61 @@ class HipEngine:
             if mode == 2 and not self._gn_epi:
                 mode = 0
             if mode > 0 or gn_stats_always:      # gn_stats_always: tests of the library's extra-statistics-launch path
-                gn_part = self.arena.alloc((batch * (oh * ow // 64) * gn_stats * 2,), torch.float32)
-                d.gn_partials, d.gn_groups = gn_part.data_ptr(), gn_stats
+                gn = self._gn_partials_out(d, batch, oh * ow, gn_stats)
+        # ---- 3. launch (and log); the hand-off tags go on once the output exists
+        self._launch(d)
+        if gn is not None:
+            out._gn = gn
+        if rs is not None:
+            out._rs = rs
+        return out
+
+    def _gn_partials_out(self, d, batch: int, hw: int, groups: int):
+        """Have the GEMM `d` (idb_gemm_desc / idb_gemm_fp8_desc) emit the first pass of the GroupNorm(groups) that reads its output
+        next; returns the ``_gn`` tag (partials, chunks, groups) for that output."""
+        part = self.arena.alloc((batch * (hw // 64) * groups * 2,), torch.float32)
+        d.gn_partials, d.gn_groups = part.data_ptr(), groups
+        return part, hw // 64, groups
+
+    def _launch(self, d) -> None:
+        """idb_gemm on `d`; with ``launch_log`` on, timed and recorded with its plan."""
         log = self.launch_log
         if log is not None:                      # bench.py's per-kernel roofline accounting (eager pass only)
             tile, sk, blocks = C.c_int32(), C.c_int32(), C.c_int32()
             L.check(self.lib.idb_gemm_plan(C.byref(d), C.byref(tile), C.byref(sk), C.byref(blocks)), "idb_gemm_plan")
             need = self.lib.idb_gemm_workspace_bytes(C.byref(d))
-            k_total = sum(ch * taps for (_, ch, taps, _, _, _) in srcs)
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
         rc = L.run_gemm(self.lib, d, self._workspace, _stream())
-        if rc == -2 and G > 1:
+        if rc == -2 and d.w_groups > 1:
             # the plan's tile height does not divide the group's rows (cross-attention K/V of 77 tokens, tiny grids): one launch per
             # (CFG half, group) on row slices — the same arithmetic
-            self._gemm_per_group(d, G, m // (self._rep * G))
+            self._gemm_per_group(d, d.w_groups, d.w_group_rows)
         else:
             L.check(rc, "idb_gemm")
-        if gn_part is not None:
-            out._gn = (gn_part, oh * ow // 64, gn_stats)
-        if rs_buf is not None:
-            out._rs = (rs_buf, nt)
         if log is not None:
             ev1.record()
-            log.append({"tile": tile.value + (1000 if gn_in is not None else 0), "split_k": sk.value, "blocks": blocks.value, "m": m, "n": n, "k": k_total,
-                        "flops": 2.0 * m * n * k_total, "ev": (ev0, ev1), "desc": d, "ws": (self._ws if need else None, need),
-                        "bytes": 2.0 * (m * k_total / (9 if srcs[0][2] == 9 else 1) + n * k_total + m * ncols)})
-        return out
+            m, n, ncols = d.batch * d.out_h * d.out_w, d.n, d.n // 2 if d.geglu else d.n
+            k_total = sum(s.channels * s.taps for s in d.src[:d.nsrc])
+            log.append({"tile": tile.value + (1000 if d.gn_in_partials else 0), "split_k": sk.value, "blocks": blocks.value, "m": m, "n": n,
+                        "k": k_total, "flops": 2.0 * m * n * k_total, "ev": (ev0, ev1), "desc": d, "ws": (self._ws if need else None, need),
+                        "bytes": 2.0 * (m * k_total / (9 if d.src[0].taps == 9 else 1) + n * k_total + m * ncols)})
 
     def _gemm_per_group(self, d, G: int, rpg: int) -> None:
-        """Fallback of the grouped-weights GEMM for plain [M][K] sources: row slice [j*rpg, (j+1)*rpg) with matrix j % G."""
+        """Fallback of the grouped-weights GEMM for plain [M][K] sources: row slice [j*rpg, (j+1)*rpg) with matrix j % G.  The
+        slices run on a copy: `d` (and its launch_log entry) keeps describing the whole launch."""
         if d.nsrc != 1 or d.src[0].taps != 1 or d.src[0].in_h != 1 or d.gn_partials or d.row_stats_out or d.ln_stats:
             raise L.IdbError("grouped weights: per-group fallback needs one plain [M][K] source without statistics outputs or a folded LayerNorm")
-        m, k, esz = d.batch, d.src[0].channels, 2
+        k, esz = d.src[0].channels, 2
         osz = 4 if d.out_dtype == L.IDB_F32 else 2
-        a0, out0, res0, w0 = d.src[0].ptr, d.out, d.residual, d.w
-        d.batch, d.w_groups = rpg, 0
-        for j in range(m // rpg):
-            d.src[0].ptr = a0 + j * rpg * k * esz
-            d.out = out0 + j * rpg * d.out_ld * osz
-            d.residual = None if not res0 else res0 + j * rpg * d.out_ld * esz
-            d.w = w0 + (j % G) * d.w_group_stride
-            L.check(L.run_gemm(self.lib, d, self._workspace, _stream()), "idb_gemm (per group)")
+        s = L.GemmDesc.from_buffer_copy(d)
+        s.batch, s.w_groups = rpg, 0
+        for j in range(d.batch // rpg):
+            s.src[0].ptr = d.src[0].ptr + j * rpg * k * esz
+            s.out = d.out + j * rpg * d.out_ld * osz
+            s.residual = d.residual + j * rpg * d.out_ld * esz if d.residual else None
+            s.w = d.w + (j % G) * d.w_group_stride
+            L.check(L.run_gemm(self.lib, s, self._workspace, _stream()), "idb_gemm (per group)")
 
     def fuses_groupnorm(self, src_shapes, w: torch.Tensor, n: int, batch: int, oh: int, ow: int, groups: int, nsrc_norm: int) -> bool:
         """Would idb_gemm apply the GroupNorm of the first `nsrc_norm` sources inside the kernel for this shape?  src_shapes:
@@ -631,9 +638,9 @@ class HipEngine:
         hit = self._gn_conv_cache.get(key)
         if hit is None:
             dummy = self._gn_ws.data_ptr()
-            d = L.gemm_desc(self.dt, [(dummy, ch, taps, oh, ow) for ch, taps in src_shapes], dummy, n, batch, oh, ow, out=dummy,
-                            w_layout=1 if getattr(w, "_tiled", None) is not None else 0, gn_in_partials=dummy, gn_in_chunks=1,
-                            gn_in_groups=groups, gn_in_eps=1e-5, gn_in_nsrc=nsrc_norm, gn_in_gamma=dummy, gn_in_beta=dummy)
+            d = self._desc([(dummy, ch, taps, oh, ow) for ch, taps in src_shapes], w, n, batch, oh, ow, w_ptr=dummy, out=dummy,
+                           gn_in_partials=dummy, gn_in_chunks=1, gn_in_groups=groups, gn_in_eps=1e-5, gn_in_nsrc=nsrc_norm,
+                           gn_in_gamma=dummy, gn_in_beta=dummy)
             hit = self._gn_conv_cache[key] = self.lib.idb_gemm_fuses_groupnorm(C.byref(d)) > 0
         return hit
 
@@ -641,28 +648,38 @@ class HipEngine:
         m = x.numel() // k
         return self.gemm([(x, k, 1, 1, 1, 0)], w, n, m, 1, 1, **kw)
 
-    def groupnorm(self, x0, c0, x1, c1, batch, hw, gamma, beta, eps, silu, groups=None) -> torch.Tensor:
-        groups = groups or self.ucfg.norm_num_groups
-        out = self.arena.alloc((batch * hw, c0 + c1), self.tdt)
-        need = self.lib.idb_groupnorm_workspace_bytes(batch, hw, groups)
-        if need > self._gn_ws.numel():
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("GroupNorm workspace would grow during graph capture")
-            self._retired.append(self._gn_ws)   # as _workspace: older graphs keep writing their partials here
-            self._gn_ws = torch.empty(need * 2, dtype=torch.uint8, device=self.device)
-        pin, pin_chunks = None, 0
+    def _take_gn(self, x0, x1, hw: int, groups: int):
+        """The statistics hand-off: (partials, chunks) that the launch which wrote x0 left on it (``_gn``) if they are the first pass of
+        GroupNorm(groups) over hw positions of x0 alone, else (None, 0).  The tag comes off either way; partials that do not fit go
+        back to the arena here, the ones returned are the caller's to free."""
         st = getattr(x0, "_gn", None)
-        if st is not None:
-            x0._gn = None
-            if x1 is None and st[1] * 64 == hw and st[2] == groups:
-                pin, pin_chunks = st[0], st[1]           # statistics produced by the GEMM that wrote x0
-        L.check(self.lib.idb_groupnorm(x0.data_ptr(), c0, _ptr(x1), c1, batch, hw, groups, eps, gamma.data_ptr(),
-                                       beta.data_ptr(), int(silu), out.data_ptr(), self.dt, self._gn_ws.data_ptr(),
-                                       self._gn_ws.numel(), _ptr(self._gn_sync), 0 if self._gn_sync is None else self._gn_sync.numel(),
-                                       _ptr(pin), pin_chunks, _stream()), "idb_groupnorm")
-        if st is not None:
-            self.arena.free(st[0])
+        if st is None:
+            return None, 0
+        x0._gn = None
+        if x1 is None and st[1] * 64 == hw and st[2] == groups:
+            return st[0], st[1]
+        self.arena.free(st[0])
+        return None, 0
+
+    def _groupnorm(self, x0, c0, x1, c1, batch, hw, gamma, beta, eps, silu, groups, x8_scale: Optional[float] = None) -> torch.Tensor:
+        """GroupNorm(+SiLU) over cat[x0, x1] in the operand dtype, or as e4m3(y / x8_scale) bytes."""
+        groups = groups or self.ucfg.norm_num_groups
+        out = self.arena.alloc((batch * hw, c0 + c1), self.tdt if x8_scale is None else torch.uint8)
+        ws = self._grown("_gn_ws", self.lib.idb_groupnorm_workspace_bytes(batch, hw, groups), 2, "GroupNorm")
+        pin, pin_chunks = self._take_gn(x0, x1, hw, groups)      # statistics produced by the GEMM that wrote x0
+        args = (x0.data_ptr(), c0, _ptr(x1), c1, batch, hw, groups, eps, gamma.data_ptr(), beta.data_ptr(), int(silu), out.data_ptr())
+        if x8_scale is None:
+            L.check(self.lib.idb_groupnorm(*args, self.dt, ws.data_ptr(), ws.numel(), _ptr(self._gn_sync),
+                                           0 if self._gn_sync is None else self._gn_sync.numel(), _ptr(pin), pin_chunks, _stream()),
+                    "idb_groupnorm")
+        else:
+            L.check(self.lib.idb_groupnorm_fp8(*args, 1.0 / x8_scale, self.dt, ws.data_ptr(), ws.numel(), _ptr(pin), pin_chunks, _stream()),
+                    "idb_groupnorm_fp8")
+        self.arena.free(pin)
         return out
+
+    def groupnorm(self, x0, c0, x1, c1, batch, hw, gamma, beta, eps, silu, groups=None) -> torch.Tensor:
+        return self._groupnorm(x0, c0, x1, c1, batch, hw, gamma, beta, eps, silu, groups)
 
     X8_SIGMAS = 8.0
 
@@ -675,36 +692,14 @@ class HipEngine:
         return float(HipEngine.X8_SIGMAS * gamma.abs().max().item() + beta.abs().max().item()) / 448.0
 
     def groupnorm_fp8(self, x0, c0, x1, c1, batch, hw, gamma, beta, eps, silu, x_scale: float, groups=None) -> torch.Tensor:
-        groups = groups or self.ucfg.norm_num_groups
-        out = self.arena.alloc((batch * hw, c0 + c1), torch.uint8)
-        need = self.lib.idb_groupnorm_workspace_bytes(batch, hw, groups)
-        if need > self._gn_ws.numel():
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("GroupNorm workspace would grow during graph capture")
-            self._retired.append(self._gn_ws)
-            self._gn_ws = torch.empty(need * 2, dtype=torch.uint8, device=self.device)
-        pin, pin_chunks = None, 0
-        st = getattr(x0, "_gn", None)
-        if st is not None:
-            x0._gn = None
-            if x1 is None and st[1] * 64 == hw and st[2] == groups:
-                pin, pin_chunks = st[0], st[1]
-        L.check(self.lib.idb_groupnorm_fp8(x0.data_ptr(), c0, _ptr(x1), c1, batch, hw, groups, eps, gamma.data_ptr(), beta.data_ptr(), int(silu),
-                                           out.data_ptr(), 1.0 / x_scale, self.dt, self._gn_ws.data_ptr(), self._gn_ws.numel(), _ptr(pin),
-                                           pin_chunks, _stream()), "idb_groupnorm_fp8")
-        if st is not None:
-            self.arena.free(st[0])
-        return out
+        return self._groupnorm(x0, c0, x1, c1, batch, hw, gamma, beta, eps, silu, groups, x_scale)
 
     def gn_statistics(self, x0, c0, x1, c1, batch, hw, groups):
         """(partials [batch][chunks][groups][2] fp32, chunks) of GroupNorm(groups) over cat[x0, x1]: taken from the launch that
         produced x0 when it emitted them (``_gn``), else one idb_groupnorm_stats launch."""
-        st = getattr(x0, "_gn", None)
-        if st is not None:
-            x0._gn = None
-            if x1 is None and st[1] * 64 == hw and st[2] == groups:
-                return st[0], st[1]
-            self.arena.free(st[0])
+        part, chunks = self._take_gn(x0, x1, hw, groups)
+        if part is not None:
+            return part, chunks
         part = self.arena.alloc((batch * 64 * groups * 2,), torch.float32)
         chunks = C.c_int32()
         L.check(self.lib.idb_groupnorm_stats(x0.data_ptr(), c0, _ptr(x1), c1, batch, hw, groups, part.data_ptr(), part.numel() * 4,
@@ -745,14 +740,13 @@ class HipEngine:
             d.sample_bias = sbias[0].data_ptr() + 4 * sbias[1]
             d.sample_bias_ld = sbias[2]
         d.residual, d.out, d.out_ld = _ptr(residual), out.data_ptr(), out.shape[-1]
-        gn_part = None
+        gn = None
         if gn_stats and self._gn_fuse and self._gn_epi and n % 160 == 0 and n % gn_stats == 0 and 160 % (n // gn_stats) == 0 and \
                 (n // gn_stats) % 2 == 0 and (oh * ow) % 64 == 0 and oh * ow <= 4096 and out.shape[-1] == n:
-            gn_part = self.arena.alloc((batch * (oh * ow // 64) * gn_stats * 2,), torch.float32)
-            d.gn_partials, d.gn_groups = gn_part.data_ptr(), gn_stats
+            gn = self._gn_partials_out(d, batch, oh * ow, gn_stats)
         L.check(self.lib.idb_gemm_fp8(C.byref(d), _stream()), "idb_gemm_fp8")
-        if gn_part is not None:
-            out._gn = (gn_part, oh * ow // 64, gn_stats)
+        if gn is not None:
+            out._gn = gn
         return out
 
     def layernorm(self, x, rows, c, gamma, beta) -> torch.Tensor:
@@ -765,15 +759,15 @@ class HipEngine:
         """LayerNorm(x) @ W^T: folded into ONE GEMM when x carries row statistics (``_rs``) and the consumer's plan runs the LDS-staged
         epilogue; else idb_layernorm + the plain GEMM.  Weights: ``{pfx}.{wname}.w`` (plain), ``.wln`` / ``.u`` / ``.v`` (folded)."""
         W = self.w
+        lw = self._Wl if wname in ("qkv", "q2") else W.__getitem__        # the LoRA-affected operands may be grouped
         rs = getattr(x, "_rs", None)
         if rs is not None and self._ln_fold:
             kf = {k: v for k, v in kw.items() if k != "bias"}          # the bias is part of .v
-            lw = self._Wl if wname in ("qkv", "q2") else W.__getitem__
             out = self.linear(x, lw(f"{pfx}.{wname}.wln"), n, c, ln=(rs[0], rs[1], lw(f"{pfx}.{wname}.u"), lw(f"{pfx}.{wname}.v"), 1e-5), **kf)
             if out is not None:
                 return out
         t = self.layernorm(x, rows, c, W[f"{pfx}.{ln_name}.g"], W[f"{pfx}.{ln_name}.b"])
-        out = self.linear(t, (self._Wl if wname in ("qkv", "q2") else W.__getitem__)(f"{pfx}.{wname}.w"), n, c, **kw)
+        out = self.linear(t, lw(f"{pfx}.{wname}.w"), n, c, **kw)
         self.arena.free(t)
         return out
 
@@ -786,8 +780,7 @@ class HipEngine:
         key = (rows, c, n, geglu)
         hit = self._fold_cache.get(key)
         if hit is None:
-            d = L.gemm_desc(self.dt, [(x.data_ptr(), c, 1, 1, 1)], x.data_ptr(), n, rows, 1, 1, geglu=int(geglu), out=x.data_ptr(),
-                            out_ld=n // 2 if geglu else n)
+            d = self._desc([(x.data_ptr(), c, 1, 1, 1)], x, n, rows, 1, 1, geglu, out=x.data_ptr())     # x stands in for the weights too
             hit = self._fold_cache[key] = self.lib.idb_gemm_folds_layernorm(C.byref(d)) > 0
         return hit
 
@@ -812,95 +805,95 @@ class HipEngine:
             self.taps[name] = t.float()          # a copy outside the arena
         return t
 
+    def _next(self, name: str, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """Module `name` turned x into y: x goes back to the arena (unless a skip connection pins it), y is the new x."""
+        self._free(x)
+        return self._tap(name, y)
+
     # ------------------------------------------------------------------------------------
     # UNet
     # ------------------------------------------------------------------------------------
+    def _norm_gemm(self, x0, c0, x1, c1, taps: int, extra, norm, w, n: int, batch: int, h: int, w_: int, fuse: bool = False, w_fused=None,
+                   fp8=None, consume: bool = False, **kw) -> torch.Tensor:
+        """GroupNorm(+SiLU) over cat[x0, x1] and the `taps`-tap GEMM [n] that consumes it, on the h x w_ grid.
+        norm = (gamma, beta, eps, silu, groups); extra: further K segments that are NOT normalised (the 1x1 shortcut sources
+        (tensor, channels, 1, h, w_, 0) of a resnet's second conv) behind the normalised one in w; kw: gemm's bias / sbias /
+        residual / gn_stats / row_stats / out...  One of three paths:
+          * fp8 = (w8, w_scale, x_scale, w_extra): idb_groupnorm_fp8 + idb_gemm_fp8; the e4m3 GEMM has one source, so the extra segments
+            run as an operand-dtype GEMM with w_extra whose result enters as the residual;
+          * fuse (the caller's permission) and the plan agrees: statistics (taken from x0's producer or one idb_groupnorm_stats launch),
+            then the GEMM whose normalizer waves apply them to the raw sources; w_fused is the weight of that form where it differs (the
+            K-split copy for two 3x3 sources);
+          * idb_groupnorm + idb_gemm over the normalised copy.  Without taps and extra segments that GEMM is a plain [M][K] linear, a
+            different descriptor from the fused 1x1 source on the grid (and planned on its own).
+        consume: x0 is dead once normalised and goes back to the arena as early as its path allows."""
+        gamma, beta, eps, silu, G = norm
+        hw, c = h * w_, c0 + c1
+        if fp8 is not None:
+            w8, s8, x_scale, w_extra = fp8
+            xn = self.groupnorm_fp8(x0, c0, x1, c1, batch, hw, gamma, beta, eps, silu, x_scale, G)
+            if consume:
+                self._free(x0)
+            res = self.gemm(extra, w_extra, n, batch, h, w_) if extra else None
+            out = self.gemm_fp8(xn, x_scale, c, taps, h, w_, w8, s8, n, batch, h, w_, **(dict(kw, residual=res) if extra else kw))
+            self.arena.free(xn)
+            self.arena.free(res)
+            return out
+        srcs = [(x0, c0, taps, h, w_, 0)] + ([(x1, c1, taps, h, w_, 0)] if x1 is not None else [])
+        wf = w if w_fused is None else w_fused
+        if fuse and self.fuses_groupnorm([(ch, t) for _, ch, t, *_ in srcs + extra], wf, n, batch, h, w_, G, len(srcs)):
+            part, chunks = self.gn_statistics(x0, c0, x1, c1, batch, hw, G)
+            out = self.gemm(srcs + extra, wf, n, batch, h, w_, gn_in=(part, chunks, G, eps, gamma, beta, silu, len(srcs)), **kw)
+            self.arena.free(part)
+            if consume:
+                self._free(x0)
+            return out
+        xn = self.groupnorm(x0, c0, x1, c1, batch, hw, gamma, beta, eps, silu, G)
+        if consume:
+            self._free(x0)
+        if taps == 1 and not extra:
+            out = self.linear(xn, w, n, c, **kw)
+        else:
+            out = self.gemm([(xn, c, taps, h, w_, 0)] + extra, w, n, batch, h, w_, **kw)
+        self.arena.free(xn)
+        return out
+
     def _resnet(self, name, xa, ca, xb, cb, cout, batch, h, w_, sbias, eps, groups=None, out_stats: bool = False) -> torch.Tensor:
         W = self.w
-        cin = ca + cb
-        G0 = groups or self.ucfg.norm_num_groups
-        short = f"{name}.has_shortcut" in W
-        if self.fp8 and f"{name}.conv1.w8" in W:
-            # fp8 MFMA path: GroupNorm+SiLU -> e4m3, conv on v_mfma_scale_f32_16x16x128_f8f6f4; the 1x1 shortcut over the raw inputs
-            # stays an f16 GEMM whose result enters the second conv as its residual
-            sb = None if sbias is None else (sbias[0], sbias[1] + self.tproj_off[name], sbias[2])
-            s1, s2 = self.x8_scale[f"{name}.gn1"], self.x8_scale[f"{name}.gn2"]
-            n1 = self.groupnorm_fp8(xa, ca, xb, cb, batch, h * w_, W[f"{name}.gn1.g"], W[f"{name}.gn1.b"], eps, True, s1, groups)
-            h1 = self.gemm_fp8(n1, s1, cin, 9, h, w_, W[f"{name}.conv1.w8"], W[f"{name}.conv1.s8"], cout, batch, h, w_,
-                               bias=W[f"{name}.conv1.b"], sbias=sb, gn_stats=G0)
-            self.arena.free(n1)
-            n2 = self.groupnorm_fp8(h1, cout, None, 0, batch, h * w_, W[f"{name}.gn2.g"], W[f"{name}.gn2.b"], eps, True, s2, groups)
-            self.arena.free(h1)
-            if short:
-                srcs = [(xa, ca, 1, h, w_, 0)] + ([(xb, cb, 1, h, w_, 0)] if xb is not None else [])
-                res = self.gemm(srcs, W[f"{name}.sc.w"], cout, batch, h, w_)
-            else:
-                res = xa
-            out = self.gemm_fp8(n2, s2, cout, 9, h, w_, W[f"{name}.conv2.w8"], W[f"{name}.conv2.s8"], cout, batch, h, w_,
-                                bias=W[f"{name}.conv2.b"], residual=res, gn_stats=G0 if out_stats else 0)
-            self.arena.free(n2)
-            if short:
-                self.arena.free(res)
-            return out
-        sb = None if sbias is None else (sbias[0], sbias[1] + self.tproj_off[name], sbias[2])
         G = groups or self.ucfg.norm_num_groups
-        hw = h * w_
-        # ---- norm1 + SiLU + conv1: inside the conv (normalizer waves) where the plan allows, else idb_groupnorm + idb_gemm
-        w1 = W.get(f"{name}.conv1.wsplit") if xb is not None else W[f"{name}.conv1.w"]
-        shapes1 = [(ca, 9)] + ([(cb, 9)] if xb is not None else [])
-        if w1 is not None and self._gn_conv_resnet and self.fuses_groupnorm(shapes1, w1, cout, batch, h, w_, G, len(shapes1)):
-            part, chunks = self.gn_statistics(xa, ca, xb, cb, batch, hw, G)
-            srcs1 = [(xa, ca, 9, h, w_, 0)] + ([(xb, cb, 9, h, w_, 0)] if xb is not None else [])
-            h1 = self.gemm(srcs1, w1, cout, batch, h, w_, bias=W[f"{name}.conv1.b"], sbias=sb, gn_stats=G,
-                           gn_in=(part, chunks, G, eps, W[f"{name}.gn1.g"], W[f"{name}.gn1.b"], True, len(srcs1)))
-            self.arena.free(part)
+        sb = None if sbias is None else (sbias[0], sbias[1] + self.tproj_off[name], sbias[2])
+        two = xb is not None
+        # fp8 MFMA path (UNet resnets of the fp8 engine): GroupNorm+SiLU -> e4m3, conv on v_mfma_scale_f32_16x16x128_f8f6f4; the 1x1
+        # shortcut over the raw inputs stays an f16 GEMM whose result enters the second conv as its residual
+        f8 = self.fp8 and f"{name}.conv1.w8" in W
+
+        def stage(i):                             # (norm, fp8) arguments of conv<i>'s _norm_gemm
+            return ((W[f"{name}.gn{i}.g"], W[f"{name}.gn{i}.b"], eps, True, G),
+                    (W[f"{name}.conv{i}.w8"], W[f"{name}.conv{i}.s8"], self.x8_scale[f"{name}.gn{i}"], W.get(f"{name}.sc.w")) if f8 else None)
+        # ---- norm1 + SiLU + conv1: inside the conv (normalizer waves) where the plan allows, else idb_groupnorm + idb_gemm.  Over
+        # cat[x, skip] (up path) the fused form reads TWO 3x3 sources and needs the K-split weight copy; norm2 consumes h1 next
+        norm, fp8 = stage(1)
+        w1f = W.get(f"{name}.conv1.wsplit") if two else W[f"{name}.conv1.w"]
+        h1 = self._norm_gemm(xa, ca, xb, cb, 9, [], norm, W[f"{name}.conv1.w"], cout, batch, h, w_, fuse=self._gn_conv_resnet and w1f is not None,
+                             w_fused=w1f, fp8=fp8, bias=W[f"{name}.conv1.b"], sbias=sb, gn_stats=G)
+        # ---- norm2 + SiLU + conv2 (+ 1x1 shortcut over the raw inputs as further K segments | + residual)
+        norm, fp8 = stage(2)
+        sc = []
+        if f"{name}.has_shortcut" in W:
+            sc = [(xa, ca, 1, h, w_, 0)] + ([(xb, cb, 1, h, w_, 0)] if two else [])
         else:
-            n1 = self.groupnorm(xa, ca, xb, cb, batch, hw, W[f"{name}.gn1.g"], W[f"{name}.gn1.b"], eps, True, groups)
-            h1 = self.gemm([(n1, cin, 9, h, w_, 0)], W[f"{name}.conv1.w"], cout, batch, h, w_, bias=W[f"{name}.conv1.b"], sbias=sb,
-                           gn_stats=G)                       # norm2 consumes h1 next
-            self.arena.free(n1)
-        # ---- norm2 + SiLU + conv2 (+ 1x1 shortcut over the raw inputs | + residual)
-        short = f"{name}.has_shortcut" in W
-        shapes2 = [(cout, 9)] + ([(ca, 1)] + ([(cb, 1)] if xb is not None else []) if short else [])
-        if self._gn_conv_resnet and self.fuses_groupnorm(shapes2, W[f"{name}.conv2.w"], cout, batch, h, w_, G, 1):
-            part, chunks = self.gn_statistics(h1, cout, None, 0, batch, hw, G)
-            srcs = [(h1, cout, 9, h, w_, 0)]
-            if short:
-                srcs += [(xa, ca, 1, h, w_, 0)] + ([(xb, cb, 1, h, w_, 0)] if xb is not None else [])
-            out = self.gemm(srcs, W[f"{name}.conv2.w"], cout, batch, h, w_, bias=W[f"{name}.conv2.b"], residual=None if short else xa,
-                            gn_stats=G if out_stats else 0, gn_in=(part, chunks, G, eps, W[f"{name}.gn2.g"], W[f"{name}.gn2.b"], True, 1))
-            self.arena.free(part)
-            self.arena.free(h1)
-            return out
-        n2 = self.groupnorm(h1, cout, None, 0, batch, hw, W[f"{name}.gn2.g"], W[f"{name}.gn2.b"], eps, True, groups)
-        self.arena.free(h1)
-        if short:
-            srcs = [(n2, cout, 9, h, w_, 0), (xa, ca, 1, h, w_, 0)]
-            if xb is not None:
-                srcs.append((xb, cb, 1, h, w_, 0))
-            out = self.gemm(srcs, W[f"{name}.conv2.w"], cout, batch, h, w_, bias=W[f"{name}.conv2.b"], gn_stats=G if out_stats else 0)
-        else:
-            assert xb is None and ca == cout
-            out = self.gemm([(n2, cout, 9, h, w_, 0)], W[f"{name}.conv2.w"], cout, batch, h, w_, bias=W[f"{name}.conv2.b"],
-                            residual=xa, gn_stats=G if out_stats else 0)
-        self.arena.free(n2)
-        return out
+            assert not two and ca == cout
+        return self._norm_gemm(h1, cout, None, 0, 9, sc, norm, W[f"{name}.conv2.w"], cout, batch, h, w_, fuse=self._gn_conv_resnet, fp8=fp8,
+                               consume=True, bias=W[f"{name}.conv2.b"], residual=None if sc else xa, gn_stats=G if out_stats else 0)
 
     def _transformer(self, a: S.AttnSpec, x, batch, h, w_, kv, n_ctx, out_stats: bool = False) -> torch.Tensor:
         W, n, c = self.w, a.name, a.channels
         hw = h * w_
         m = batch * hw
         G = self.ucfg.norm_num_groups
-        if c <= self._gn_conv_max_c and self.fuses_groupnorm([(c, 1)], W[f"{n}.proj_in.w"], c, batch, h, w_, G, 1):
-            # Transformer2DModel.norm (no SiLU) inside proj_in
-            part, chunks = self.gn_statistics(x, c, None, 0, batch, hw, G)
-            h0 = self.gemm([(x, c, 1, h, w_, 0)], W[f"{n}.proj_in.w"], c, batch, h, w_, bias=W[f"{n}.proj_in.b"],
-                           row_stats=self.folds(x, m, c, 3 * c), gn_in=(part, chunks, G, 1e-6, W[f"{n}.norm.g"], W[f"{n}.norm.b"], False, 1))
-            self.arena.free(part)
-        else:
-            xn = self.groupnorm(x, c, None, 0, batch, hw, W[f"{n}.norm.g"], W[f"{n}.norm.b"], 1e-6, False)
-            h0 = self.linear(xn, W[f"{n}.proj_in.w"], c, c, bias=W[f"{n}.proj_in.b"], row_stats=self.folds(xn, m, c, 3 * c))
-            self.arena.free(xn)
+        # Transformer2DModel.norm (no SiLU) + proj_in: inside proj_in up to _gn_conv_max_c channels
+        h0 = self._norm_gemm(x, c, None, 0, 1, [], (W[f"{n}.norm.g"], W[f"{n}.norm.b"], 1e-6, False, G), W[f"{n}.proj_in.w"], c, batch, h, w_,
+                             fuse=c <= self._gn_conv_max_c, bias=W[f"{n}.proj_in.b"], row_stats=self.folds(x, m, c, 3 * c))
         # self-attention
         qkv = self.ln_linear(h0, m, c, n, "ln1", "qkv", 3 * c)
         self._free_rs(h0)
@@ -951,14 +944,17 @@ class HipEngine:
         self.arena.free(h3)
         return out
 
-    def cross_kv(self, ctx: torch.Tensor, batch: int, n_ctx: int) -> Dict[str, torch.Tensor]:
+    def cross_kv(self, ctx: torch.Tensor, batch: int, n_ctx: int, in_arena: bool = False) -> Dict[str, torch.Tensor]:
         """ctx: [batch*n_ctx, cross_dim] operand dtype -> per attention module [batch, n_ctx, 2C]
-        (to_k | to_v of attn2; constant over the sampling loop)."""
+        (to_k | to_v of attn2; constant over the sampling loop).  in_arena: pinned arena blocks (the sampling loop, capturable)
+        instead of tensors of their own."""
         out = {}
         cd = self.ucfg.cross_attention_dim
         for a in self._attn_specs:
-            t = torch.empty((batch * n_ctx, 2 * a.channels), dtype=self.tdt, device=self.device)
+            t = None if in_arena else torch.empty((batch * n_ctx, 2 * a.channels), dtype=self.tdt, device=self.device)
             out[a.name] = self.linear(ctx, self._Wl(f"{a.name}.kv2.w"), 2 * a.channels, cd, out=t)
+            if in_arena:
+                self._pinned.add(out[a.name].data_ptr())
         return out
 
     def time_tables(self, timesteps: torch.Tensor) -> torch.Tensor:
@@ -1008,30 +1004,26 @@ class HipEngine:
                 last = j == len(blk["resnets"]) - 1
                 y = self._resnet(r.name, x, r.cin, None, 0, r.cout, B, h, w_, sbias, eps_n,
                                  out_stats=bool(blk["attns"]) or not (last and blk["down"]))
-                self._free(x)
-                x, ch = self._tap(r.name, y), r.cout
+                x, ch = self._next(r.name, x, y), r.cout
                 if blk["attns"]:
                     y = self._transformer(blk["attns"][j], x, B, h, w_, kv[blk["attns"][j].name], n_ctx, out_stats=not (last and blk["down"]))
-                    self._free(x)
-                    x = self._tap(blk["attns"][j].name, y)
+                    x = self._next(blk["attns"][j].name, x, y)
                 skips.append((x, ch))
                 self._pinned.add(x.data_ptr())
             if blk["down"]:
                 y = self.gemm([(x, ch, 9, h, w_, 0)], W[blk["down"] + ".w"], ch, B, h // 2, w_ // 2,
                               bias=W[blk["down"] + ".b"], stride=2, gn_stats=cfg.norm_num_groups)   # next: a resnet's norm1
                 h, w_ = h // 2, w_ // 2
-                x = self._tap(blk["down"], y)
+                x = self._next(blk["down"], x, y)
                 skips.append((x, ch))
                 self._pinned.add(x.data_ptr())
         m = g.mid
         y = self._resnet(m["resnets"][0].name, x, ch, None, 0, ch, B, h, w_, sbias, eps_n, out_stats=True)
-        x = self._tap(m["resnets"][0].name, y)          # previous x is the last skip: stays pinned
+        x = self._next(m["resnets"][0].name, x, y)      # previous x is the last skip: stays pinned
         y = self._transformer(m["attn"], x, B, h, w_, kv[m["attn"].name], n_ctx, out_stats=True)
-        self._free(x)
-        x = self._tap(m["attn"].name, y)
+        x = self._next(m["attn"].name, x, y)
         y = self._resnet(m["resnets"][1].name, x, ch, None, 0, ch, B, h, w_, sbias, eps_n)
-        self._free(x)
-        x = self._tap(m["resnets"][1].name, y)
+        x = self._next(m["resnets"][1].name, x, y)
         for bi, blk in enumerate(g.up):
             for j, r in enumerate(blk["resnets"]):
                 sk, sc = skips.pop()
@@ -1039,24 +1031,18 @@ class HipEngine:
                 y = self._resnet(r.name, x, ch, sk, sc, r.cout, B, h, w_, sbias, eps_n, out_stats=bool(blk["attns"]))
                 self._pinned.discard(sk.data_ptr())
                 self.arena.free(sk)
-                self._free(x)
-                x, ch = self._tap(r.name, y), r.cout
+                x, ch = self._next(r.name, x, y), r.cout
                 if blk["attns"]:
                     final = bi == len(g.up) - 1 and j == len(blk["resnets"]) - 1 and not blk["up"]     # next: conv_norm_out
                     y = self._transformer(blk["attns"][j], x, B, h, w_, kv[blk["attns"][j].name], n_ctx, out_stats=final)
-                    self._free(x)
-                    x = self._tap(blk["attns"][j].name, y)
+                    x = self._next(blk["attns"][j].name, x, y)
             if blk["up"]:
                 y = self.gemm([(x, ch, 9, h, w_, 1)], W[blk["up"] + ".w"], ch, B, 2 * h, 2 * w_, bias=W[blk["up"] + ".b"])
-                self._free(x)
-                x = self._tap(blk["up"], y)
+                x = self._next(blk["up"], x, y)
                 h, w_ = 2 * h, 2 * w_
         assert not skips
-        n = self.groupnorm(x, ch, None, 0, B, h * w_, W["conv_norm_out.g"], W["conv_norm_out.b"], eps_n, True)
-        self._free(x)
-        eps = self.gemm([(n, ch, 9, h, w_, 0)], W["conv_out.w"], cfg.out_channels, B, h, w_, bias=W["conv_out.b"],
-                        out_f32=True, out=eps_out)
-        self.arena.free(n)
+        eps = self._norm_gemm(x, ch, None, 0, 9, [], (W["conv_norm_out.g"], W["conv_norm_out.b"], eps_n, True, cfg.norm_num_groups), W["conv_out.w"],
+                              cfg.out_channels, B, h, w_, consume=True, bias=W["conv_out.b"], out_f32=True, out=eps_out)
         self.last_forward_launches = int(self.lib.idb_launch_count() - launches0)     # kernels of ONE (CFG) UNet forward
         return eps
 
@@ -1106,11 +1092,7 @@ class HipEngine:
             hist.zero_()                                     # multistep solver: x0 history (coefficient 0 on the first step)
         ctx = self.arena.alloc(tuple(ctx_f32.shape), self.tdt)
         L.check(self.lib.idb_cast_f32(ctx_f32.data_ptr(), ctx.data_ptr(), ctx_f32.numel(), self.dt, _stream()), "idb_cast_f32")
-        kv = {}
-        cd = self.ucfg.cross_attention_dim
-        for a in self._attn_specs:
-            kv[a.name] = self.linear(ctx, self._Wl(f"{a.name}.kv2.w"), 2 * a.channels, cd)
-            self._pinned.add(kv[a.name].data_ptr())
+        kv = self.cross_kv(ctx, rep * B, n_ctx, in_arena=True)
         self.arena.free(ctx)
         for i in range(steps):
             self.unet_nhwc(lat, rep, (tp, i * self.tproj_total, 0), kv, n_ctx, eps_out=eps)
@@ -1160,23 +1142,23 @@ class HipEngine:
         coefs = coefs.to(self.device).float().contiguous()
         ts = torch.tensor([float(t) for t in timesteps], dtype=torch.float32, device=self.device)
         tp = self.time_tables(ts)
+
+        def loop_buffers() -> dict:               # latents, the UNet's output, the multistep x0 / PLMS eps history
+            f32 = dict(dtype=torch.float32, device=self.device)
+            return {"lat": torch.empty((B, lc, h, w_), **f32), "eps": torch.empty((rep * B * h * w_, self.ucfg.out_channels), **f32),
+                    "hist": torch.empty((n_hist, B, lc, h, w_), **f32) if multistep else None}
         if not use_graph or trace is not None:
-            lat = torch.empty((B, lc, h, w_), dtype=torch.float32, device=self.device)
-            eps = torch.empty((rep * B * h * w_, self.ucfg.out_channels), dtype=torch.float32, device=self.device)
-            hist = torch.empty((n_hist, B, lc, h, w_), dtype=torch.float32, device=self.device) if multistep else None
-            self._sample_body(ctx_f32, noise, coefs, tp, lat, eps, steps, rep, n_ctx, vpred, trace, hist, plms)
-            return lat
+            b = loop_buffers()
+            self._sample_body(ctx_f32, noise, coefs, tp, b["lat"], b["eps"], steps, rep, n_ctx, vpred, trace, b["hist"], plms)
+            return b["lat"]
         if not hasattr(self, "_graphs"):
             self._graphs = {}
         key = ("sample", B, lc, h, w_, steps, n_ctx, cfg_on, vpred, self.dtype_name, multistep, self.groups)
         ent = self._graphs.get(key)
         if ent is None:
-            ent = {"ctx": ctx_f32.clone(), "noise": noise.clone(), "coefs": coefs.clone(), "tp": tp.clone(),
-                   "lat": torch.empty((B, lc, h, w_), dtype=torch.float32, device=self.device),
-                   "eps": torch.empty((rep * B * h * w_, self.ucfg.out_channels), dtype=torch.float32, device=self.device)}
             # every buffer the captured graph references lives in `ent` (the multistep x0 / PLMS eps history too: a local here
             # would go back to the caching allocator while replays keep writing through its address)
-            ent["hist"] = torch.empty((n_hist, B, lc, h, w_), dtype=torch.float32, device=self.device) if multistep else None
+            ent = {"ctx": ctx_f32.clone(), "noise": noise.clone(), "coefs": coefs.clone(), "tp": tp.clone(), **loop_buffers()}
             args = (ent["ctx"], ent["noise"], ent["coefs"], ent["tp"], ent["lat"], ent["eps"], steps, rep, n_ctx, vpred, None,
                     ent["hist"], plms)
             self._sample_body(*args)                     # eager warm-up: allocates every arena block, sets func attributes
@@ -1196,7 +1178,29 @@ class HipEngine:
     # ------------------------------------------------------------------------------------
     # VAE decoder (AutoencoderKL.decode -> Decoder.forward)
     # ------------------------------------------------------------------------------------
-    def _vae_attention(self, x, batch, h, w_, c, a: str = "decoder.mid_block.attentions.0") -> torch.Tensor:
+    def _vae_mid(self, side: str, x, c, B, h, w_) -> torch.Tensor:
+        """`side`.mid_block (side: "decoder" / "encoder"): resnet, single-head attention, resnet; x goes back to the arena."""
+        G, eps_n = self.vcfg.norm_num_groups, self.vcfg.norm_eps
+        y = self._resnet(f"{side}.mid_block.resnets.0", x, c, None, 0, c, B, h, w_, None, eps_n, G)
+        self.arena.free(x)
+        x = self._vae_attention(y, B, h, w_, c, f"{side}.mid_block.attentions.0")
+        self.arena.free(y)
+        y = self._resnet(f"{side}.mid_block.resnets.1", x, c, None, 0, c, B, h, w_, None, eps_n, G)
+        self.arena.free(x)
+        return y
+
+    def _vae_chunks(self, x: torch.Tensor, chunk: int, run):
+        """The chunked VAE entry points: per `chunk` samples of x a fresh arena, yielding (sample slice, run(samples), how many); the
+        result goes back to the arena when the caller has dealt with it."""
+        for b0 in range(0, x.shape[0], chunk):
+            self.arena.reset()
+            self._pinned.clear()
+            xb = x[b0:b0 + chunk].contiguous()
+            y = run(xb)
+            yield slice(b0, b0 + chunk), y, xb.shape[0]
+            self.arena.free(y)
+
+    def _vae_attention(self, x, batch, h, w_, c, a: str) -> torch.Tensor:
         W = self.w
         hw = h * w_
         G = self.vcfg.norm_num_groups
@@ -1204,7 +1208,6 @@ class HipEngine:
         q = self.linear(xn, W[f"{a}.q.w"], c, c, bias=W[f"{a}.q.b"])
         k = self.linear(xn, W[f"{a}.k.w"], c, c, bias=W[f"{a}.k.b"])
         o = self.arena.alloc((batch * hw, c), self.tdt)
-        esz = 2
         for b in range(batch):
             xb = xn[b * hw:(b + 1) * hw]
             # V^T[c][token] = Wv x^T (bias folded in after P V: rows of P sum to 1)
@@ -1232,13 +1235,7 @@ class HipEngine:
         L.check(self.lib.idb_conv_in(z.data_ptr(), W["v.conv_in.w"].data_ptr(), W["v.conv_in.b"].data_ptr(), x.data_ptr(), B, 1,
                                      lc, h, w_, cm, float(in_scale), W["v.pq.w"].data_ptr(), W["v.pq.b"].data_ptr(), self.dt,
                                      _stream()), "idb_conv_in")
-        y = self._resnet("decoder.mid_block.resnets.0", x, cm, None, 0, cm, B, h, w_, None, eps_n, G)
-        self.arena.free(x)
-        x = self._vae_attention(y, B, h, w_, cm)
-        self.arena.free(y)
-        y = self._resnet("decoder.mid_block.resnets.1", x, cm, None, 0, cm, B, h, w_, None, eps_n, G)
-        self.arena.free(x)
-        x, ch = y, cm
+        x, ch = self._vae_mid("decoder", x, cm, B, h, w_), cm
         for blk in g.up:
             for name, cin, cout in blk["resnets"]:
                 y = self._resnet(name, x, cin, None, 0, cout, B, h, w_, None, eps_n, G)
@@ -1249,12 +1246,8 @@ class HipEngine:
                 self.arena.free(x)
                 x = y
                 h, w_ = 2 * h, 2 * w_
-        n = self.groupnorm(x, ch, None, 0, B, h * w_, W["v.norm_out.g"], W["v.norm_out.b"], eps_n, True, G)
-        self.arena.free(x)
-        img = self.gemm([(n, ch, 9, h, w_, 0)], W["v.conv_out.w"], cfg.out_channels, B, h, w_, bias=W["v.conv_out.b"],
-                        out_f32=True)
-        self.arena.free(n)
-        return img
+        return self._norm_gemm(x, ch, None, 0, 9, [], (W["v.norm_out.g"], W["v.norm_out.b"], eps_n, True, G), W["v.conv_out.w"], cfg.out_channels,
+                               B, h, w_, consume=True, bias=W["v.conv_out.b"], out_f32=True)
 
     # ------------------------------------------------------------------------------------
     # VAE encoder (AutoencoderKL.encode -> Encoder.forward + quant_conv; train_ID-Booth.py:1001)
@@ -1284,18 +1277,9 @@ class HipEngine:
                 self.arena.free(cur)
                 cur = y
                 h, w_ = h // 2, w_ // 2
-        y = self._resnet("encoder.mid_block.resnets.0", cur, ch, None, 0, ch, B, h, w_, None, eps_n, G)
-        self.arena.free(cur)
-        cur = self._vae_attention(y, B, h, w_, ch, "encoder.mid_block.attentions.0")
-        self.arena.free(y)
-        y = self._resnet("encoder.mid_block.resnets.1", cur, ch, None, 0, ch, B, h, w_, None, eps_n, G)
-        self.arena.free(cur)
-        n = self.groupnorm(y, ch, None, 0, B, h * w_, W["ve.norm_out.g"], W["ve.norm_out.b"], eps_n, True, G)
-        self.arena.free(y)
-        mom = self.gemm([(n, ch, 9, h, w_, 0)], W["ve.conv_out.w"], 2 * cfg.latent_channels, B, h, w_, bias=W["ve.conv_out.b"],
-                        out_f32=True)
-        self.arena.free(n)
-        return mom
+        y = self._vae_mid("encoder", cur, ch, B, h, w_)
+        return self._norm_gemm(y, ch, None, 0, 9, [], (W["ve.norm_out.g"], W["ve.norm_out.b"], eps_n, True, G), W["ve.conv_out.w"],
+                               2 * cfg.latent_channels, B, h, w_, consume=True, bias=W["ve.conv_out.b"], out_f32=True)
 
     def vae_encode(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None, scale: float = 1.0, chunk: int = 4):
         """``vae.encode(x).latent_dist``: returns (latents, mean, logvar), NCHW fp32.  latents = (mean + std * noise) * scale
@@ -1311,15 +1295,9 @@ class HipEngine:
         nz = None if noise is None else noise.to(device=self.device, dtype=torch.float32).contiguous()
         if nz is not None and tuple(nz.shape) != tuple(lat.shape):
             raise ValueError(f"noise must have shape {tuple(lat.shape)}")
-        for b0 in range(0, B, chunk):
-            self.arena.reset()
-            self._pinned.clear()
-            xb = x[b0:b0 + chunk].contiguous()
-            mom = self.vae_encode_nhwc(xb)
-            L.check(self.lib.idb_vae_sample(mom.data_ptr(), None if nz is None else nz[b0:b0 + chunk].data_ptr(), float(scale),
-                                            lat[b0:b0 + chunk].data_ptr(), mean[b0:b0 + chunk].data_ptr(),
-                                            logvar[b0:b0 + chunk].data_ptr(), xb.shape[0], lc, h * w_, _stream()), "idb_vae_sample")
-            self.arena.free(mom)
+        for sl, mom, nb in self._vae_chunks(x, chunk, self.vae_encode_nhwc):
+            L.check(self.lib.idb_vae_sample(mom.data_ptr(), None if nz is None else nz[sl].data_ptr(), float(scale), lat[sl].data_ptr(),
+                                            mean[sl].data_ptr(), logvar[sl].data_ptr(), nb, lc, h * w_, _stream()), "idb_vae_sample")
         return lat, mean, logvar
 
     def vae_decode(self, z: torch.Tensor, in_scale: float = 1.0, chunk: int = 4):
@@ -1330,14 +1308,8 @@ class HipEngine:
         H, Wd = h * up, w_ * up
         oc = self.vcfg.out_channels
         out = torch.empty((B, oc, H, Wd), dtype=torch.float32, device=self.device)
-        for b0 in range(0, B, chunk):
-            self.arena.reset()
-            self._pinned.clear()
-            zb = z[b0:b0 + chunk].contiguous()
-            img = self.vae_decode_nhwc(zb, in_scale)
-            L.check(self.lib.idb_f32_nhwc_to_nchw(img.data_ptr(), out[b0:b0 + chunk].data_ptr(), zb.shape[0], H * Wd, oc,
-                                                  _stream()), "idb_f32_nhwc_to_nchw")
-            self.arena.free(img)
+        for sl, img, nb in self._vae_chunks(z, chunk, lambda zb: self.vae_decode_nhwc(zb, in_scale)):
+            L.check(self.lib.idb_f32_nhwc_to_nchw(img.data_ptr(), out[sl].data_ptr(), nb, H * Wd, oc, _stream()), "idb_f32_nhwc_to_nchw")
         return out
 
     def decode_images(self, latents: torch.Tensor, chunk: int = 4, want_u8: bool = True):
@@ -1350,15 +1322,9 @@ class HipEngine:
         oc = self.vcfg.out_channels
         img01 = torch.empty((B, H, Wd, oc), dtype=torch.float32, device=self.device)
         u8 = torch.empty((B, H, Wd, oc), dtype=torch.uint8, device=self.device) if want_u8 else None
-        for b0 in range(0, B, chunk):
-            self.arena.reset()
-            self._pinned.clear()
-            zb = latents[b0:b0 + chunk].contiguous()
-            img = self.vae_decode_nhwc(zb, 1.0 / self.vcfg.scaling_factor)
-            L.check(self.lib.idb_postprocess(img.data_ptr(), img01[b0:b0 + chunk].data_ptr(),
-                                             _ptr(u8[b0:b0 + chunk]) if want_u8 else None, img.numel(), _stream()),
+        for sl, img, _ in self._vae_chunks(latents, chunk, lambda zb: self.vae_decode_nhwc(zb, 1.0 / self.vcfg.scaling_factor)):
+            L.check(self.lib.idb_postprocess(img.data_ptr(), img01[sl].data_ptr(), _ptr(u8[sl]) if want_u8 else None, img.numel(), _stream()),
                     "idb_postprocess")
-            self.arena.free(img)
         return img01, u8
 
 

@@ -1047,12 +1047,19 @@ def test_grouped_weights_gemm_in_one_launch_and_per_group(eng, rpg, launches):
     wg = torch.stack([t.reshape(-1) for t in mats])
     wg._groups, wg._tiled = G, (n, k)
     prev, eng._rep = eng._rep, rep
+    eng.launch_log = []
     try:
         before = eng.lib.idb_launch_count()
         out = eng.gemm([(a, k, 1, 1, 1, 0)], wg, n, m, 1, 1, bias=bias, row_stats=True)
         assert eng.lib.idb_launch_count() - before == launches
+        (entry,) = eng.launch_log
     finally:
         eng._rep = prev
+        eng.launch_log = None
+    # the logged descriptor describes the whole launch, also where it ran slice by slice
+    desc = entry["desc"]
+    assert desc.batch == m and desc.w_groups == G
+    assert desc.src[0].ptr == a.data_ptr() and desc.out == out.data_ptr()
     for j in range(rep * G):
         rows = slice(j * rpg, (j + 1) * rpg)
         ref = eng.gemm([(a[rows], k, 1, 1, 1, 0)], mats[j % G], n, rpg, 1, 1, bias=bias)
