@@ -42,6 +42,7 @@ EXPORTS = [
     "idb_resize_linear_u8", "idb_fiqa_tail",
     "idb_diffuse_targets", "idb_objective_workspace_bytes", "idb_objective_mse_x0", "idb_crop_resize_bilinear_f32", "idb_crop_resize_area_f32",
     "idb_identity_losses",
+    "idb_randaug",
 ]
 
 
@@ -174,6 +175,7 @@ def load() -> C.CDLL:
         "idb_crop_resize_bilinear_f32": (C.c_int, [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp]),
         "idb_crop_resize_area_f32": (C.c_int, [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, f32, f32, vp]),
         "idb_identity_losses": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "idb_randaug": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

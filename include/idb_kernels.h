@@ -671,6 +671,28 @@ int idb_crop_resize_area_f32(const float* src, int32_t batch, int32_t h, int32_t
 int idb_identity_losses(const float* feat, const float* pos, const float* neg, int32_t n, int32_t d, float* cos, float* identity,
                         float* triplet, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The FR-training input stage (ID-Booth's FR_training/utils/augmentation.py:49-54 `aug_rand_4_16` and its kin: RandomHorizontalFlip ->
+ * RandAugment -> ToTensor -> Normalize(0.5, 0.5), applied there per PIL image inside DataLoader workers, utils/dataset.py:154-196).
+ * Validates its arguments before any HIP call and never synchronises.
+ *   idb_randaug: replaces `img.transpose(FLIP_LEFT_RIGHT)`, the op chain of FR_training/utils/rand_augment.py:_apply_op (:69-152, the
+ *       13 ops of :191-210 on PIL images, interpolation NEAREST, fill None) and `ToTensor()` + `normalize`, for a uint8 RGB batch
+ *       in [n][h][w][3] in ONE launch: one workgroup per image, the image in LDS for the whole chain.  flip: uint8 [n] (NULL: no flip).
+ *       Slot s of image i is (slot_op[i * num_ops + s], slot_iarg[(i * num_ops + s) * 6 ...], slot_farg[i * num_ops + s]); op ids in the
+ *       reference's dict order: 0 Identity, 1 ShearX, 2 TranslateX, 3 Rotate, 4 Brightness, 5 Color, 6 Contrast, 7 Sharpness,
+ *       8 Posterize, 9 Solarize, 10 AutoContrast, 11 Equalize, 12 Grayscale (any other id is Identity).  The host (augment.slot_tables)
+ *       supplies: for 1-3 the six 16.16 integers a0..a5 of Pillow's affine_fixed (source = ((a2 + a1 y + a0 x) >> 16, (a5 + a4 y + a3 x)
+ *       >> 16), black outside; every read is range-checked); for 4-7 farg = the blend factor 1 + magnitude (Image.blend in float32
+ *       against black / luma / the mean luma / ImageFilter.SMOOTH, no FMA); for 8 iarg[0] = the bit mask; for 9 farg = the threshold.
+ *       10 and 11 build their per-channel LUTs from an LDS histogram (integer atomics, a fixed-order prefix sum; the AutoContrast
+ *       LUT in double): bit-identical from run to run.  out_u8: uint8 [n][h][w][3] (the augmented image) or NULL; out_f32_nchw: fp32
+ *       [n][3][h][w] = ((x / 255) - 0.5) / 0.5, each step rounded once, or NULL; at least one.  num_ops >= 0 (0: flip and conversion only;
+ *       the slot pointers may then be NULL).  n >= 1, h, w >= 8: IDB_EINVAL otherwise.  h * w * 3 > 49152 bytes (128 x 128): IDB_EUNSUPPORTED
+ *       — two image buffers plus the tables must fit the LDS of a CU.  `in` is only read.  Slot arrays and out_f32_nchw 4-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int idb_randaug(const uint8_t* in, int32_t n, int32_t h, int32_t w, const uint8_t* flip, const int32_t* slot_op, const int32_t* slot_iarg,
+                const float* slot_farg, int32_t num_ops, uint8_t* out_u8, float* out_f32_nchw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
