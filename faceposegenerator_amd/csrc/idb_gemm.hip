@@ -22,6 +22,11 @@
 //   * grids smaller than the chip (the whole batch-1 UNet) use split-K sized to one workgroup per
 //     CU, fp32 slabs + a reduce/epilogue launch (deterministic, no atomics) that can also emit the
 //     first GroupNorm pass of its output.
+//   * the launch geometry is resolved on the host (idb_gemm_epi.h: GemmParams, idb_fill_geometry; idb_fastdiv.h): no kernel of the
+//     ring / loader-wave / fused-GroupNorm / patch families divides by a run-time value in front of its first load — tile index,
+//     K range of a split, K seek and row decode are multiply-highs by exact reciprocals or shifts, the patch conv's H / nimg / RI
+//     and the GroupNorm's group width arrive as values (a batch-1 launch is ~14 us, and 7-12 division expansions stood on every
+//     loader wave's path to its first LDS-DMA).  Quotients, and with them every address and K range, are what they were.
 #include "idb_common.h"
 #include <stdlib.h>
 
@@ -54,6 +59,8 @@ __global__ __launch_bounds__(128 * WM, 2) void idb_gemm_kernel_relu(const GemmPa
 // of idb_gemm_kernel (results are bit-identical) but execute only barrier -> ds_read -> MFMA.  Both roles pass ONE s_barrier per
 // K-step (no flags, no polling: every wave reaches the same nk barriers), the loaders leave after the loop — s_barrier counts only
 // the surviving waves of a workgroup — and the compute waves run the shared epilogue among themselves.
+//   prologue: the A half of stage 0 is requested first — K seek, row decode, first tap's offsets — and the weight descriptor, the weight
+//   offsets and the grouped-weight arithmetic, which only the W half needs, behind it; the loads of a stage keep their order and count.
 //   ring: NS stages; at the top of K-step `it` the loaders wait until stage `it` has landed (counted vmcnt: stages it+1 ..
 //   it+NS-2 stay in flight), the barrier publishes it and proves stage it-1 is read, then they issue stage it+NS-1 into that buffer.
 // ------------------------------------------------------------------------------------------------------------
@@ -74,28 +81,12 @@ __device__ __forceinline__ void idb_gemm_kernel_lw_body(const GemmParams& p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool loader = wave >= 2 * WM;                        // wave-uniform (readfirstlane): a scalar branch, not an EXEC mask
 
-    int wg, kz;
-    if (p.xcd_mode == 0) {
-        const int nwg = gridDim.x, orig = blockIdx.x;
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-        wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-        kz = blockIdx.z;
-    } else {
-        const int X = gridDim.x;
-        const int lin = blockIdx.x + X * blockIdx.z;
-        const int xcd = lin & 7, j = lin >> 3;
-        if (p.xcd_mode == 1) {
-            kz = xcd + 8 * (j / X);
-            wg = j % X;
-        } else {
-            kz = xcd >> 1;
-            wg = (xcd & 1) * (X >> 1) + j;
-        }
-    }
-    const int tm = wg / p.tiles_n, tn = wg - tm * p.tiles_n;
+    int wg, kz, tm, tn;
+    idb_wg_tile(p, wg, kz);
+    idb_tile_mn(p, wg, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
-    const int kt0 = (int)(((long long)kz * p.ktiles) / p.splitk);
-    const int kt1 = (int)(((long long)(kz + 1) * p.ktiles) / p.splitk);
+    int kt0, kt1;
+    idb_k_range(p, kz, kt0, kt1);
     const int nk = kt1 - kt0;
 
     if (loader) {
@@ -104,55 +95,24 @@ __device__ __forceinline__ void idb_gemm_kernel_lw_body(const GemmParams& p) {
         const int lt = tid - CT;                               // 0 .. 64*LW-1
         const int lrow = lt >> 3;                              // 0 .. LR-1
         const unsigned cg16 = ((lt & 7) ^ (lrow & 7)) * 16;    // swizzle on the source side (LR is a multiple of 8)
+        // First DMA first: the A half of stage 0 is requested as soon as the K seek and the row decode allow; the weight offsets, the
+        // weight descriptor and the grouped-weight arithmetic — which only the W half needs — come behind it.
+        int s, tap, c0, cur_c = 64, tap_end = 9;
+        idb_k_seek(p, kt0, s, tap, c0);
         int a_b[NA], a_oy[NA], a_ox[NA];
         bool a_ok[NA];
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int m = m0 + i * LR + lrow;
             a_ok[i] = m < p.M;
-            const int mm = a_ok[i] ? m : 0;
-            if (p.HW == 1) {
-                a_b[i] = mm;
-                a_oy[i] = a_ox[i] = 0;
-            } else {
-                a_b[i] = mm / p.HW;
-                const int rem = mm - a_b[i] * p.HW;
-                a_oy[i] = rem / p.OW;
-                a_ox[i] = rem - a_oy[i] * p.OW;
-            }
+            idb_row_decode(p, a_ok[i] ? m : 0, a_b[i], a_oy[i], a_ox[i]);
         }
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w + idb_weight_group(p, m0) * p.w_group_stride), 0, p.w_bytes, IDB_RSRC_FLAGS);
-        unsigned w_voff[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int n = n0 + j * LR + lrow;
-            w_voff[j] = (n < p.N && j * LR + lrow < BN) ? (unsigned)(n >> 4) * p.w_blk_bytes + (unsigned)(n & 15) * p.w_row_bytes + cg16 : IDB_OOB;
-        }
+        __amdgpu_buffer_rsrc_t rs_a, rs_w;
+        unsigned a_voff[NA], w_voff[NJ];
         unsigned w_soff = (unsigned)kt0 * p.w_kstep;
-        int s = 0, tap = 0, c0 = 0, cur_c = 64, tap_end = 9;
-        {
-            int rem = kt0;
-            while (s < IDB_MAX_SRC - 1) {
-                const int steps = p.src[s].taps * (p.src[s].C >> 6);
-                if (rem < steps) break;
-                rem -= steps;
-                ++s;
-            }
-            const int cs = p.src[s].C >> 6;
-            if (p.src[s].taps == 9) {
-                tap = rem / cs;
-                c0 = (rem - tap * cs) << 6;
-            } else {
-                tap = 4;
-                c0 = rem << 6;
-            }
-        }
-        __amdgpu_buffer_rsrc_t rs_a = rs_w;
-        unsigned a_voff[NA];
         bool need_retap = true;
-        auto stage = [&](int buf) {
+        auto stage_a = [&](int buf) {
             char* sA = smem + buf * STAGE;
-            char* sB = sA + BM * 128;
             if (need_retap) {
                 const GemmSrcK S = p.src[s];
                 rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)S.ptr, 0, S.bytes, IDB_RSRC_FLAGS);
@@ -174,6 +134,9 @@ __device__ __forceinline__ void idb_gemm_kernel_lw_body(const GemmParams& p) {
 #pragma unroll
             for (int i = 0; i < NA; ++i)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, LDS_PTR(sA + (i * 64 * LW + lw * 64) * 16), 16, a_voff[i], a_soff, 0, 0);
+        };
+        auto stage_w = [&](int buf) {                          // the W half, and on to the next K-step
+            char* sB = smem + buf * STAGE + BM * 128;
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, LDS_PTR(sB + (j * 64 * LW + lw * 64) * 16), 16, w_voff[j], w_soff, 0, 0);
@@ -188,8 +151,20 @@ __device__ __forceinline__ void idb_gemm_kernel_lw_body(const GemmParams& p) {
                 }
             }
         };
+        if (nk > 0) stage_a(0);
+        rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w + idb_weight_group(p, m0) * p.w_group_stride), 0, p.w_bytes, IDB_RSRC_FLAGS);
 #pragma unroll
-        for (int st = 0; st < NS - 1; ++st)
+        for (int j = 0; j < NJ; ++j) {
+            const int n = n0 + j * LR + lrow;
+            w_voff[j] = (n < p.N && j * LR + lrow < BN) ? (unsigned)(n >> 4) * p.w_blk_bytes + (unsigned)(n & 15) * p.w_row_bytes + cg16 : IDB_OOB;
+        }
+        if (nk > 0) stage_w(0);
+        auto stage = [&](int buf) {
+            stage_a(buf);
+            stage_w(buf);
+        };
+#pragma unroll
+        for (int st = 1; st < NS - 1; ++st)
             if (st < nk) stage(st);
         int cur = 0;
         for (int it = 0; it < nk; ++it) {
@@ -333,14 +308,15 @@ __global__ __launch_bounds__(128 * WM + 64 * LW) void idb_gemm_kernel_lw_relu(co
 __device__ __forceinline__ void idb_patch_seek(const GemmParams& p, int g, int& s, int& c, int& t, int& base) {
     s = 0;
     base = 0;
-    while (s < IDB_MAX_SRC - 1 && g >= p.src[s].taps * (p.src[s].C >> 6)) {
-        const int steps = p.src[s].taps * (p.src[s].C >> 6);
+    while (s < IDB_MAX_SRC - 1 && g >= p.src[s].steps) {
+        const int steps = p.src[s].steps;
         g -= steps;
         base += steps;
         ++s;
     }
-    c = g / p.src[s].taps;
-    t = g - c * p.src[s].taps;
+    const int taps = p.src[s].taps;                            // 9 or 1: a division by a literal is a multiply-high
+    c = taps == 9 ? g / 9 : g;
+    t = g - c * taps;
 }
 
 // GN = true pieces shared by the transforming patch loaders and the MFMA waves that help with the first patch (below).
@@ -357,7 +333,7 @@ __device__ __forceinline__ void idb_gn_part_load(const GemmParams& p, int b0, in
 
 // {mean, rstd} of those groups into gst: the pixel-chunk partials are added in gn_apply_kernel's order
 __device__ __forceinline__ void idb_gn_part_finish(const GemmParams& p, float2* gst, int pw, int lane, const f32x2 (&pv)[8]) {
-    const int G = p.gn_in_groups, cpg = p.gn_in_c / G;
+    const int G = p.gn_in_groups, cpg = p.gn_in_cpg;
     const int g = min(pw * 8 + (lane >> 3), G - 1), sub = lane & 7;
     float a = 0.f, q = 0.f;
 #pragma unroll
@@ -437,35 +413,21 @@ __global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const Ge
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int wg, kz;
-    if (p.xcd_mode == 0) {
-        const int nwg = gridDim.x, orig = blockIdx.x;
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-        wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-        kz = blockIdx.z;
-    } else {                                                   // one K-slice per XCD (group): see idb_gemm_kernel
-        const int X = gridDim.x;
-        const int lin = blockIdx.x + X * blockIdx.z;
-        const int xcd = lin & 7, j = lin >> 3;
-        if (p.xcd_mode == 1) {
-            kz = xcd + 8 * (j / X);
-            wg = j % X;
-        } else {
-            kz = xcd >> 1;
-            wg = (xcd & 1) * (X >> 1) + j;
-        }
-    }
-    const int tm = wg / p.tiles_n, tn = wg - tm * p.tiles_n;
+    int wg, kz, tm, tn;
+    idb_wg_tile(p, wg, kz);
+    idb_tile_mn(p, wg, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     // this workgroup's K range in K-steps of the chunk-major walk (balanced; a split may start and end inside a chunk)
-    const int g0 = (int)(((long long)kz * p.ktiles) / p.splitk), g1 = (int)(((long long)(kz + 1) * p.ktiles) / p.splitk);
+    int g0, g1;
+    idb_k_range(p, kz, g0, g1);
     const int nk = g1 - g0;
     int s0, c0, t0, base0;
     idb_patch_seek(p, g0, s0, c0, t0, base0);
     // tile geometry: R image rows of width W; nimg whole images when the image is smaller than the tile
-    const int W = p.OW, H = p.HW / W;
-    const int nimg = p.HW >= BM ? 1 : BM / p.HW;
-    const int RI = BM / W / nimg;                              // tile rows per image
+    // (resolved on the host for this variant's BM: idb_fill_geometry)
+    const int W = p.OW, H = p.pc_H;
+    [[maybe_unused]] const int nimg = p.pc_nimg;
+    const int RI = p.pc_RI;                                    // tile rows per image
 
     // GN, the prologue (everything in front of the first MFMA) runs on all twelve non-weight waves:
     //   * MFMA waves 0-3 load the producer's partial sums at once and turn them into {mean, rstd} per group (gst) in front of barrier S,
@@ -491,12 +453,13 @@ __global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const Ge
 
     if constexpr (GN) {
         const int q8 = lane >> 3;
-        const int b0 = m0 / p.HW, y0 = (m0 - b0 * p.HW) / W;
-        const int G = p.gn_in_groups, cpg = p.gn_in_c / G;
-        const unsigned rcpg = 0xFFFFFFFFu / (unsigned)cpg + 1u;   // ceil(2^32 / cpg) for cpg > 1 (idb_gn_coeffs)
+        int b0, y0, x0;
+        idb_row_decode(p, m0, b0, y0, x0);
+        const int cpg = p.gn_in_cpg;
+        const unsigned rcpg = p.gn_in_rcpg;                    // ceil(2^32 / cpg) for cpg > 1 (idb_gn_coeffs)
         const int co = (lane & 7) ^ q8;                        // this lane's channel octet inside every chunk (pixel q has q & 7 == q8)
         const int PW = W + 2, PP = (RI + 2) * PW;
-        const unsigned rpw = (65536u + PW - 1) / PW;           // q / PW == (q * rpw) >> 16: q < 288, PW <= 66, so q * (rpw * PW - 65536) < 65536
+        const unsigned rpw = p.pc_rpw;                         // ceil(2^16 / PW): q / PW == (q * rpw) >> 16: q < 288, PW <= 66, so q * (rpw * PW - 65536) < 65536
         // patch pixel q -> offset of this lane's 16 bytes in a source of C channels (IDB_OOB: outside the image or behind the patch's last pixel)
         auto pix_voff = [&](int q, int C, bool& ok) -> unsigned {
             const int pr = (int)(((unsigned)q * rpw) >> 16), px = q - pr * PW;
@@ -606,7 +569,8 @@ __global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const Ge
         // ---------------- patch loaders ----------------
         const int pw = wave - 10;
         const int q8 = lane >> 3;
-        const int b0 = m0 / p.HW, y0 = (m0 - b0 * p.HW) / W;
+        int b0, y0, x0;
+        idb_row_decode(p, m0, b0, y0, x0);
         unsigned voff[NPI];
         int seg = -1, npi = 0;
         __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.src[0].ptr, 0, p.src[0].bytes, IDB_RSRC_FLAGS);
@@ -620,8 +584,8 @@ __global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const Ge
 #pragma unroll
             for (int i = 0; i < NPI; ++i) {
                 const int q = (i * 2 + pw) * 8 + q8;
-                const int pr = q / PW, px = q - pr * PW;
-                const int img = pr / RIh, lr = pr - img * RIh;
+                const int pr = idb_fd_div(q, p.fd_pw[h]), px = q - pr * PW;
+                const int img = idb_fd_div(pr, p.fd_rih[h]), lr = pr - img * RIh;
                 const int y = y0 + lr - h, x = px - h;
                 const bool ok = q < PP && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
                 const int pix = ((b0 + img) * H + y) * W + x;
@@ -710,9 +674,9 @@ __global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const Ge
 #pragma unroll
     for (int i = 0; i < MF; ++i) {
         const int ml = wm * 16 * MF + i * 16 + fr;
-        const int r = ml / W;
+        const int r = idb_fd_div(ml, p.fd_ow);
         xx[i] = ml - r * W;
-        rr[i] = r + 2 * (r / RI);                              // + 2 halo rows per image in front (9-tap segments only)
+        rr[i] = r + 2 * idb_fd_div(r, p.fd_rih[0]);                              // + 2 halo rows per image in front (9-tap segments only)
     }
     // K-step state (segment s, chunk c, tap t) and the half-step rotation around the barrier of idb_gemm_kernel_lw: the second 32-deep
     // half of a K-step is read before the barrier that publishes the next one and multiplied behind it
@@ -843,55 +807,23 @@ __global__ __launch_bounds__(128 * WM + 256 + 64 * NV) void idb_gemm_kernel_gn(c
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* tab = (float2*)(smem + NS * STAGE);                // [nsamp][gn_in_c] {k, h}
     const int hw_s = p.HW;
-    const int nsamp = BM > hw_s ? BM / hw_s : 1;               // host: HW % BM == 0 or BM % HW == 0
+    const int nsamp = p.gn_in_nsamp;                           // BM > HW ? BM / HW : 1 (host: HW % BM == 0 or BM % HW == 0)
     float2* gstat = tab + nsamp * p.gn_in_c;                   // [nsamp][groups] {mean, rstd}
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    int wg, kz;
-    if (p.xcd_mode == 0) {
-        const int nwg = gridDim.x, orig = blockIdx.x;
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-        wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-        kz = blockIdx.z;
-    } else {
-        const int X = gridDim.x;
-        const int lin = blockIdx.x + X * blockIdx.z;
-        const int xcd = lin & 7, j = lin >> 3;
-        if (p.xcd_mode == 1) {
-            kz = xcd + 8 * (j / X);
-            wg = j % X;
-        } else {
-            kz = xcd >> 1;
-            wg = (xcd & 1) * (X >> 1) + j;
-        }
-    }
-    const int tm = wg / p.tiles_n, tn = wg - tm * p.tiles_n;
+    int wg, kz, tm, tn;
+    idb_wg_tile(p, wg, kz);
+    idb_tile_mn(p, wg, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
-    const int kt0 = (int)(((long long)kz * p.ktiles) / p.splitk);
-    const int kt1 = (int)(((long long)(kz + 1) * p.ktiles) / p.splitk);
+    int kt0, kt1;
+    idb_k_range(p, kz, kt0, kt1);
     const int nk = kt1 - kt0;
 
     // K-step cursor shared by loaders and normalizers: source s, tap, channel offset c0
-    int s = 0, tap = 0, c0 = 0;
-    {
-        int rem = kt0;
-        while (s < IDB_MAX_SRC - 1) {
-            const int steps = p.src[s].taps * (p.src[s].C >> 6);
-            if (rem < steps) break;
-            rem -= steps;
-            ++s;
-        }
-        const int cs = p.src[s].C >> 6;
-        if (p.src[s].taps == 9) {
-            tap = rem / cs;
-            c0 = (rem - tap * cs) << 6;
-        } else {
-            tap = 4;
-            c0 = rem << 6;
-        }
-    }
+    int s, tap, c0;
+    idb_k_seek(p, kt0, s, tap, c0);
     auto advance = [&]() {                                     // to the next K-step
         c0 += 64;
         if (c0 == p.src[s].C) {
@@ -906,14 +838,14 @@ __global__ __launch_bounds__(128 * WM + 256 + 64 * NV) void idb_gemm_kernel_gn(c
     if (wave >= 2 * WM + LW) {
         // ---------------- normalizer waves ----------------
         const int nt = tid - CT - LT;
-        const int b_first = m0 / hw_s;
-        const int G = p.gn_in_groups, cpg = p.gn_in_c / G;
+        const int b_first = idb_fd_div(m0, p.fd_hw);
+        const int G = p.gn_in_groups, cpg = p.gn_in_cpg;
         // phase 1: {mean, rstd} per (sample, group): 8 lanes per pair add the pixel-chunk partials in gn_apply_kernel's order
         for (int pr0 = 0; pr0 < nsamp * G; pr0 += VT / 8) {
             const int pr = pr0 + (nt >> 3), sub = nt & 7;
             const int prc = min(pr, nsamp * G - 1);
-            const int sm = prc / G, g = prc - sm * G;
-            const int b = min(b_first + sm, (p.M - 1) / hw_s);
+            const int sm = idb_fd_div(prc, p.fd_gn_g), g = prc - sm * G;
+            const int b = min(b_first + sm, p.gn_in_last_b);
             f32x2 pv[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -944,8 +876,8 @@ __global__ __launch_bounds__(128 * WM + 256 + 64 * NV) void idb_gemm_kernel_gn(c
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                     // barrier A
         // phase 2: k = rstd * gamma, h = beta - mean * k per (sample, channel)
         for (int i = nt; i < nsamp * p.gn_in_c; i += VT) {
-            const int sm = i / p.gn_in_c, c = i - sm * p.gn_in_c;
-            const float2 st = gstat[sm * G + c / cpg];
+            const int sm = idb_fd_div(i, p.fd_gn_c), c = i - sm * p.gn_in_c;
+            const float2 st = gstat[sm * G + idb_fd_div(c, p.fd_gn_cpg)];
             const float k = st.y * p.gn_in_gamma[c];
             tab[i] = make_float2(k, p.gn_in_beta[c] - st.x * k);
         }
@@ -957,11 +889,7 @@ __global__ __launch_bounds__(128 * WM + 256 + 64 * NV) void idb_gemm_kernel_gn(c
             const int row = j * (VT / 8) + (nt >> 3);
             const int m = m0 + row;
             r_ok[j] = m < p.M;
-            const int mm = r_ok[j] ? m : 0;
-            r_b[j] = mm / hw_s;
-            const int rem = mm - r_b[j] * hw_s;
-            r_oy[j] = rem / p.OW;
-            r_ox[j] = rem - r_oy[j] * p.OW;
+            idb_row_decode(p, r_ok[j] ? m : 0, r_b[j], r_oy[j], r_ox[j]);
             r_b[j] -= b_first;
         }
         int cb = 0;                                            // first channel of source s inside the normalised concatenation
@@ -1029,11 +957,7 @@ __global__ __launch_bounds__(128 * WM + 256 + 64 * NV) void idb_gemm_kernel_gn(c
         for (int i = 0; i < NA; ++i) {
             const int m = m0 + i * LR + lrow;
             a_ok[i] = m < p.M;
-            const int mm = a_ok[i] ? m : 0;
-            a_b[i] = mm / p.HW;
-            const int rem = mm - a_b[i] * p.HW;
-            a_oy[i] = rem / p.OW;
-            a_ox[i] = rem - a_oy[i] * p.OW;
+            idb_row_decode(p, a_ok[i] ? m : 0, a_b[i], a_oy[i], a_ox[i]);
         }
         const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w + idb_weight_group(p, m0) * p.w_group_stride), 0, p.w_bytes, IDB_RSRC_FLAGS);
         unsigned w_voff[NJ];
@@ -1155,12 +1079,13 @@ __global__ __launch_bounds__(256, 2) void idb_gemm_kernel_rs(const GemmParams p)
     const int nwg = gridDim.x, orig = blockIdx.x;
     const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
     const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-    const int tm = wg / p.tiles_n, tn = wg - tm * p.tiles_n;
+    int tm, tn;
+    idb_tile_mn(p, wg, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
 
     const int kz = blockIdx.z;
-    const int kt0 = (int)(((long long)kz * p.ktiles) / p.splitk);
-    const int kt1 = (int)(((long long)(kz + 1) * p.ktiles) / p.splitk);
+    int kt0, kt1;
+    idb_k_range(p, kz, kt0, kt1);
     const int nk = kt1 - kt0;
 
     // thread stages chunk (tid&7) of rows (tid>>3)+32i: global chunk c lands at LDS chunk position c ^ (row&7)
@@ -1173,16 +1098,7 @@ __global__ __launch_bounds__(256, 2) void idb_gemm_kernel_rs(const GemmParams p)
     for (int i = 0; i < MF; ++i) {
         const int m = m0 + i * 32 + lrow;
         a_ok[i] = m < p.M;
-        const int mm = a_ok[i] ? m : 0;
-        if (p.HW == 1) {
-            a_b[i] = mm;
-            a_oy[i] = a_ox[i] = 0;
-        } else {
-            a_b[i] = mm / p.HW;
-            const int rem = mm - a_b[i] * p.HW;
-            a_oy[i] = rem / p.OW;
-            a_ox[i] = rem - a_oy[i] * p.OW;
-        }
+        idb_row_decode(p, a_ok[i] ? m : 0, a_b[i], a_oy[i], a_ox[i]);
     }
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w + idb_weight_group(p, m0) * p.w_group_stride), 0, p.w_bytes, IDB_RSRC_FLAGS);
     unsigned w_voff[NF];
@@ -1193,24 +1109,8 @@ __global__ __launch_bounds__(256, 2) void idb_gemm_kernel_rs(const GemmParams p)
     }
     unsigned w_soff = (unsigned)kt0 * p.w_kstep;
 
-    int s = 0, tap = 0, c0 = 0, cur_c = 64, tap_end = 9;
-    {
-        int rem = kt0;
-        while (s < IDB_MAX_SRC - 1) {
-            const int steps = p.src[s].taps * (p.src[s].C >> 6);
-            if (rem < steps) break;
-            rem -= steps;
-            ++s;
-        }
-        const int cs = p.src[s].C >> 6;
-        if (p.src[s].taps == 9) {
-            tap = rem / cs;
-            c0 = (rem - tap * cs) << 6;
-        } else {
-            tap = 4;
-            c0 = rem << 6;
-        }
-    }
+    int s, tap, c0, cur_c = 64, tap_end = 9;
+    idb_k_seek(p, kt0, s, tap, c0);
     __amdgpu_buffer_rsrc_t rs_a = rs_w;
     unsigned a_voff[MF];
     bool need_retap = true;
@@ -2298,6 +2198,8 @@ extern "C" int idb_gemm(const idb_gemm_desc* d, void* workspace, size_t workspac
         // the reduce launch will be idb_splitk_reduce_gn_kernel: same conditions and slice width as launch_all computes
         if (idb_reduce_vec_ok(p, d->n)) p.slab_swc = gn_reduce_slice(d->n, d->gn_groups);
     }
+    // everything the kernels would otherwise divide for (idb_gemm_epi.h: GemmParams)
+    IDB_REQUIRE(idb_fill_geometry(p, (long long)pl.tiles_m * pl.tiles_n, pl.v->bm), "idb_gemm: grid or K range beyond 2^31 (tiles, split_k * K-steps)");
     hipStream_t st = (hipStream_t)stream;
     return d->dtype == IDB_BF16 ? launch_all<__bf16>(d, p, pl, st) : launch_all<_Float16>(d, p, pl, st);
 }

@@ -460,6 +460,7 @@ extern "C" int idb_gemm_fp8(const idb_gemm_fp8_desc* d, void* stream) {
     const bool big = env_big > 0 && g.ktiles >= 10 && ((M + 255) / 256) * g.tiles_n >= env_big;
     const int bm = big ? 256 : 128;
     const int tiles = (int)((M + bm - 1) / bm) * g.tiles_n;
+    IDB_REQUIRE(idb_fill_geometry(g, tiles, bm), "idb_gemm_fp8: grid beyond 2^31 tiles");     // the shared epilogue's divisions (GemmParams)
     hipStream_t st = (hipStream_t)stream;
     bool gn_after = false;                 // first GroupNorm pass of the output: from the shared LDS-staged epilogue when it can
     if (d->gn_partials) {

@@ -2,23 +2,63 @@
 // (LDS-staged coalesced / direct / split-K slabs) and the split-K reduce launches.  Moved out of idb_gemm.hip unchanged.
 #pragma once
 #include "idb_common.h"
+#include "idb_fastdiv.h"
 #include <stdlib.h>
 
 struct GemmSrcK {
     const char* ptr;
     unsigned bytes;   // tensor size in bytes = buffer num_records (< 2^31, checked on the host)
     int C, taps, H, W, up;
+    int steps;            // K-steps of this source = taps * (C / 64): what the K seeks subtract        } idb_fill_geometry
+    idb_fastdiv fd_cs;    // division by C / 64 (numerator < 9 C / 64: the tap of a K-step)            }
 };
 
+// The launch geometry is resolved ONCE, on the host (idb_fill_geometry): every quotient a kernel prologue or epilogue needs whose
+// divisor is fixed by the launch comes in as a value (H, nimg, RI, cpg, ...), or as an idb_fastdiv record (idb_fastdiv.h: multiply-high
+// by an exact reciprocal, or a shift).  The kernels hold no division by a run-time value in front of their first load: each was
+// 25-40 instructions (100+ for the 64-bit K ranges), recomputed by every workgroup of every launch — 7-12 of them on the loader
+// waves' path to the first LDS-DMA.
+// Layout: the scalars a loader wave reads before its first DMA stand together at the head (kernel arguments arrive through scalar
+// loads of up to 16 consecutive dwords: neighbours share a load and its wait), the sources behind them, the epilogue's operands last.
 struct GemmParams {
-    GemmSrcK src[IDB_MAX_SRC];
+    // ---- tile and K range of the workgroup, row decode, weight addressing
     int M, N, HW, OW, stride, pad;
+    int tiles_n, ktiles, splitk;
+    int xcd_mode;   // 0: tiles dealt to XCDs in runs, K-split on grid z; 1/2: one K-slice per XCD (group), see idb_gemm_kernel
+    idb_fastdiv fd_tiles_n;          // tile index / tiles_n
+    idb_fastdiv fd_splitk;           // kz * ktiles / splitk: the K ranges stay floor(kz ktiles / splitk) .. floor((kz + 1) ktiles / splitk)
+    idb_fastdiv fd_gx;               // xcd_mode 1: (linear id >> 3) / gridDim.x
+    idb_fastdiv fd_hw, fd_ow;        // m / HW, (m % HW) / OW
     unsigned w_row_bytes, w_bytes;   // w_row_bytes: bytes between consecutive weight rows inside a 16-row block
     unsigned w_blk_bytes, w_kstep;   // bytes between 16-row blocks / between K-steps of one row (idb_gemm_desc.w_layout; idb_gemm kernels only)
-    int ktiles, kt_per_split, splitk;
-    int slab_swc;   // 0: split-K slabs are [z][M][N] row-major; else [z][M/64][N/swc][64][swc] blocks = the windows of idb_splitk_reduce_gn_kernel
-    int xcd_mode;   // 0: tiles dealt to XCDs in runs, K-split on grid z; 1/2: one K-slice per XCD (group), see idb_gemm_kernel
     const char* w;
+    // grouped weights (idb_gemm_desc.w_groups): tile rows [m0, m0 + BM) use matrix (m0 / w_group_rows) % w_groups
+    int w_groups, w_group_rows;
+    long long w_group_stride;
+    idb_fastdiv fd_wgr, fd_wg;       // m0 / w_group_rows, that / w_groups
+    GemmSrcK src[IDB_MAX_SRC];
+    // ---- patch-resident conv (idb_conv_patch_kernel), for the variant's row tile: image height, whole images per tile (1 when the
+    // image is larger than the tile), tile rows per image; divisions by the patch width OW + 2h and by RI + 2h (h = 1: 3x3 halo)
+    int pc_H, pc_nimg, pc_RI;
+    unsigned pc_rpw;                 // ceil(2^16 / (OW + 2)): q / (OW + 2) == (q * pc_rpw) >> 16 for the fused-GroupNorm patch (q < 288, OW + 2 <= 66)
+    idb_fastdiv fd_pw[2], fd_rih[2];
+    // ---- GroupNorm(+SiLU) of the first gn_nsrc sources applied by normalizer waves inside the kernel (idb_gemm_kernel_gn) or by the
+    // transforming patch loaders: statistics as idb_groupnorm's partials_in over the channel concatenation of those sources, gamma /
+    // beta over the same channels
+    const float* gn_in_part;
+    const float* gn_in_gamma;
+    const float* gn_in_beta;
+    int gn_in_chunks, gn_in_groups, gn_in_nsrc, gn_in_silu, gn_in_c;      // gn_in_c: channels of the normalised concatenation
+    float gn_in_eps;
+    int gn_in_cpg;                   // gn_in_c / gn_in_groups
+    unsigned gn_in_rcpg;             // ceil(2^32 / gn_in_cpg) (idb_gn_coeffs; unused for gn_in_cpg == 1)
+    int gn_in_nsamp, gn_in_last_b;   // idb_gemm_kernel_gn: samples per row tile (>= 1), (M - 1) / HW
+    idb_fastdiv fd_gn_g, fd_gn_c, fd_gn_cpg;   // divisions by gn_in_groups, gn_in_c, gn_in_cpg
+    // ---- epilogue
+    int kt_per_split;
+    int slab_swc;   // 0: split-K slabs are [z][M][N] row-major; else [z][M/64][N/swc][64][swc] blocks = the windows of idb_splitk_reduce_gn_kernel
+    int slab_nb;    // N / slab_swc
+    idb_fastdiv fd_swc;
     const float* bias;
     const float* sbias;
     int sbias_ld;
@@ -27,7 +67,6 @@ struct GemmParams {
     int out_ld, out_f32, geglu;
     float scale;
     float* partial;
-    int tiles_n;
     int dbg_skip_store, lds_epi, act, dbg_loop;   // dbg_* are read only by the profiling build (IDB_PROFILING, `make prof`)
     unsigned* counters;   // non-null: in-kernel split-K reduce
     unsigned out_bytes;   // persistent variant: size of the output tensor (buffer range check drops masked stores)
@@ -43,20 +82,122 @@ struct GemmParams {
     // the tile's column range holds whole groups (host: idb_epilogue_emits_gn)
     float* gn_part;
     int gn_groups;
-    // grouped weights (idb_gemm_desc.w_groups): tile rows [m0, m0 + BM) use matrix (m0 / w_group_rows) % w_groups
-    int w_groups, w_group_rows;
-    long long w_group_stride;
-    // GroupNorm(+SiLU) of the first gn_nsrc sources applied by normalizer waves inside the kernel (idb_gemm_kernel_gn): statistics as
-    // idb_groupnorm's partials_in over the channel concatenation of those sources, gamma / beta over the same channels
-    const float* gn_in_part;
-    const float* gn_in_gamma;
-    const float* gn_in_beta;
-    int gn_in_chunks, gn_in_groups, gn_in_nsrc, gn_in_silu, gn_in_c;      // gn_in_c: channels of the normalised concatenation
-    float gn_in_eps;
 };
 
+// Host: everything of GemmParams that is derived from the launch's sizes.  Call once M, N, HW, OW, tiles_n, ktiles, splitk, src[],
+// w_groups / w_group_rows, gn_in_* and slab_swc are set; `tiles` = workgroups per K slice (gridDim.x), bm = the variant's row tile.
+// The numerator ranges are the ones the callers check: M, the tile count and splitk * ktiles are all < 2^31.  false: out of range.
+inline bool idb_fill_geometry(GemmParams& p, long long tiles, int bm) {
+    bool ok = true, k;
+    const long long kmax = (long long)p.splitk * p.ktiles;
+    if (p.M < 1 || p.HW < 1 || p.OW < 1 || p.tiles_n < 1 || p.splitk < 1 || tiles < 1 || tiles >= (1LL << 31) || kmax >= (1LL << 31)) return false;
+    const uint32_t mmax = (uint32_t)p.M - 1u;
+    p.fd_tiles_n = idb_fastdiv_make((uint32_t)p.tiles_n, (uint32_t)tiles, &k), ok &= k;
+    p.fd_splitk = idb_fastdiv_make((uint32_t)p.splitk, (uint32_t)kmax, &k), ok &= k;
+    p.fd_gx = idb_fastdiv_make((uint32_t)tiles, 0x7FFFFFFFu, &k), ok &= k;
+    p.fd_hw = idb_fastdiv_make((uint32_t)p.HW, 0x7FFFFFFFu, &k), ok &= k;     // also rows past M of the last tile
+    p.fd_ow = idb_fastdiv_make((uint32_t)p.OW, 0x7FFFFFFFu, &k), ok &= k;
+    const uint32_t gr = p.w_groups > 1 && p.w_group_rows > 0 ? (uint32_t)p.w_group_rows : 1u;
+    p.fd_wgr = idb_fastdiv_make(gr, 0x7FFFFFFFu, &k), ok &= k;
+    p.fd_wg = idb_fastdiv_make(p.w_groups > 1 ? (uint32_t)p.w_groups : 1u, 0x7FFFFFFFu, &k), ok &= k;
+    for (int s = 0; s < IDB_MAX_SRC; ++s) {
+        const int cs = p.src[s].C >> 6;
+        p.src[s].steps = p.src[s].taps * cs;
+        p.src[s].fd_cs = idb_fastdiv_make(cs > 0 ? (uint32_t)cs : 1u, (uint32_t)(9 * (cs > 0 ? cs : 1)), &k), ok &= k;
+    }
+    p.pc_H = p.HW / p.OW;
+    p.pc_nimg = p.HW >= bm ? 1 : bm / p.HW;
+    p.pc_RI = bm / p.OW / p.pc_nimg;
+    if (p.pc_RI < 1) p.pc_RI = 1;                                             // not a patch shape: unused
+    p.pc_rpw = (65536u + (unsigned)p.OW + 1u) / ((unsigned)p.OW + 2u);
+    for (int h = 0; h < 2; ++h) {
+        p.fd_pw[h] = idb_fastdiv_make((uint32_t)(p.OW + 2 * h), 0xFFFFu, &k), ok &= k;
+        p.fd_rih[h] = idb_fastdiv_make((uint32_t)(p.pc_RI + 2 * h), 0xFFFFu, &k), ok &= k;
+    }
+    const int g = p.gn_in_groups > 0 ? p.gn_in_groups : 1, gc = p.gn_in_c > 0 ? p.gn_in_c : 1;
+    p.gn_in_cpg = gc / g > 0 ? gc / g : 1;
+    p.gn_in_rcpg = 0xFFFFFFFFu / (unsigned)p.gn_in_cpg + 1u;
+    p.gn_in_nsamp = bm > p.HW ? bm / p.HW : 1;
+    p.gn_in_last_b = (int)(mmax / (uint32_t)p.HW);
+    p.fd_gn_g = idb_fastdiv_make((uint32_t)g, 0x7FFFFFFFu, &k), ok &= k;
+    p.fd_gn_c = idb_fastdiv_make((uint32_t)gc, 0x7FFFFFFFu, &k), ok &= k;
+    p.fd_gn_cpg = idb_fastdiv_make((uint32_t)p.gn_in_cpg, 0x7FFFFFFFu, &k), ok &= k;
+    const int swc = p.slab_swc > 0 ? p.slab_swc : 1;
+    p.slab_nb = p.N / swc;
+    p.fd_swc = idb_fastdiv_make((uint32_t)swc, 0x7FFFFFFFu, &k), ok &= k;
+    return ok;
+}
+
+// ---- device side of the resolved geometry (shared by every implicit-GEMM kernel) -------------------------------------------
+// workgroup -> output tile wg and K slice kz: the XCD-aware bijective remaps described at idb_gemm_kernel
+__device__ __forceinline__ void idb_wg_tile(const GemmParams& p, int& wg, int& kz) {
+    if (p.xcd_mode == 0) {
+        const int nwg = gridDim.x, orig = blockIdx.x;
+        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
+        wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+        kz = blockIdx.z;
+    } else {
+        const int X = gridDim.x;
+        const int lin = blockIdx.x + X * blockIdx.z;
+        const int xcd = lin & 7, j = lin >> 3;
+        if (p.xcd_mode == 1) {
+            const int jq = idb_fd_div(j, p.fd_gx);
+            kz = xcd + 8 * jq;
+            wg = j - jq * X;
+        } else {
+            kz = xcd >> 1;
+            wg = (xcd & 1) * (X >> 1) + j;
+        }
+    }
+}
+
+// tile -> (row tile, column tile)
+__device__ __forceinline__ void idb_tile_mn(const GemmParams& p, int wg, int& tm, int& tn) {
+    tm = idb_fd_div(wg, p.fd_tiles_n);
+    tn = wg - tm * p.tiles_n;
+}
+
+// K range of slice kz in K-steps: the balanced partition floor(kz ktiles / splitk) .. floor((kz + 1) ktiles / splitk) (slice sizes
+// differ by at most one); kz * ktiles < 2^31 (host), so the products need no 64-bit arithmetic
+__device__ __forceinline__ void idb_k_range(const GemmParams& p, int kz, int& kt0, int& kt1) {
+    const int a = kz * p.ktiles;
+    kt0 = idb_fd_div(a, p.fd_splitk);
+    kt1 = idb_fd_div(a + p.ktiles, p.fd_splitk);
+}
+
+// K-step kt of the tap-major K walk ([source][tap][channel chunk]) -> source s, tap (a 1x1 source sits on the centre tap 4), channel offset c0
+__device__ __forceinline__ void idb_k_seek(const GemmParams& p, int kt, int& s, int& tap, int& c0) {
+    int rem = kt;
+    s = 0;
+    while (s < IDB_MAX_SRC - 1) {
+        const int steps = p.src[s].steps;
+        if (rem < steps) break;
+        rem -= steps;
+        ++s;
+    }
+    if (p.src[s].taps == 9) {
+        tap = idb_fd_div(rem, p.src[s].fd_cs);
+        c0 = (rem - tap * (p.src[s].C >> 6)) << 6;
+    } else {
+        tap = 4;
+        c0 = rem << 6;
+    }
+}
+
+// output row m -> (sample, y, x); HW == 1 (a plain [M][K] matrix) comes out as (m, 0, 0) through the same shifts
+__device__ __forceinline__ void idb_row_decode(const GemmParams& p, int m, int& b, int& oy, int& ox) {
+    b = idb_fd_div(m, p.fd_hw);
+    const int rem = m - b * p.HW;
+    oy = idb_fd_div(rem, p.fd_ow);
+    ox = rem - oy * p.OW;
+}
+
 // byte offset of the weight matrix (and element offset of its folded-LayerNorm vectors) a tile uses
-__device__ __forceinline__ int idb_weight_group(const GemmParams& p, int m0) { return p.w_groups > 1 ? (m0 / p.w_group_rows) % p.w_groups : 0; }
+__device__ __forceinline__ int idb_weight_group(const GemmParams& p, int m0) {
+    if (p.w_groups <= 1) return 0;
+    const int q = idb_fd_div(m0, p.fd_wgr);
+    return q - idb_fd_div(q, p.fd_wg) * p.w_groups;
+}
 
 // voffset of a lane that must read zeros: beyond num_records of every descriptor (all < 2^31), and
 // voffset + soffset cannot wrap, whichever of the two the hardware range check looks at.
@@ -136,11 +277,12 @@ template <int NF, int BM>
 __device__ __forceinline__ void idb_load_colvecs(const GemmParams& p, int m0, int n0, int wn, int fg, f32x4 (&ca)[NF], f32x4 (&cb)[NF]) {
     const bool ln = p.ln_stats != nullptr;
     const int m_last = min(m0 + BM, p.M) - 1;
-    const bool sb_tile = p.sbias && (m0 / p.HW == m_last / p.HW);
+    const int b_first = idb_fd_div(m0, p.fd_hw);
+    const bool sb_tile = p.sbias && (b_first == idb_fd_div(m_last, p.fd_hw));
     const float* dummy = (const float*)p.w;
     const long long go = (long long)idb_weight_group(p, m0) * p.N;           // grouped weights: one (u, v) pair per group
     const float* pa = ln ? p.ln_v + go : p.bias;
-    const float* pb = ln ? p.ln_u + go : (sb_tile ? p.sbias + (long long)(m0 / p.HW) * p.sbias_ld : nullptr);
+    const float* pb = ln ? p.ln_u + go : (sb_tile ? p.sbias + (long long)b_first * p.sbias_ld : nullptr);
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
         const int nc = min(n0 + (wn * NF + j) * 16 + fg * 4, p.N - 4);
@@ -182,13 +324,13 @@ __device__ __forceinline__ void idb_lds_epilogue(const GemmParams& p, char* smem
     }
     // ca / cb: idb_load_colvecs (raw values; which terms exist is decided here)
     const int m_last = min(m0 + BM, p.M) - 1;
-    const bool sb_tile = p.sbias && (m0 / p.HW == m_last / p.HW);      // else (HW < BM): per-row loads below
+    const bool sb_tile = p.sbias && (idb_fd_div(m0, p.fd_hw) == idb_fd_div(m_last, p.fd_hw));      // else (HW < BM): per-row loads below
     const bool has_a = rowtab || p.bias, has_b = rowtab || sb_tile;
 #pragma unroll
     for (int i = 0; i < MF; ++i) {
         const int row = (wm * MF + i) * 16 + fr;
         const int mc = min(m0 + row, p.M - 1);
-        const float* sb = (p.sbias && !sb_tile) ? p.sbias + (long long)(mc / p.HW) * p.sbias_ld : nullptr;
+        const float* sb = (p.sbias && !sb_tile) ? p.sbias + (long long)idb_fd_div(mc, p.fd_hw) * p.sbias_ld : nullptr;
         const float2 mr = rowtab ? rowtab[row] : make_float2(0.f, 1.f);
         // folded LayerNorm: rstd (scale acc - mean u) + v = rs acc + kb u + v;  otherwise scale acc + bias + per-sample bias
         const float rs = mr.y * p.scale, kb = rowtab ? -mr.x * mr.y : 1.f;
@@ -310,7 +452,7 @@ __device__ __forceinline__ void idb_lds_epilogue(const GemmParams& p, char* smem
                     q += __shfl_xor(q, o, 64);
                 }
                 if (sub == 0 && live) {
-                    const int mrow = m0 + c * 64, b = mrow / p.HW, chunk = (mrow - b * p.HW) >> 6;
+                    const int mrow = m0 + c * 64, b = idb_fd_div(mrow, p.fd_hw), chunk = (mrow - b * p.HW) >> 6;
                     float* dst = p.gn_part + (((long long)b * (p.HW >> 6) + chunk) * p.gn_groups + n0 / cpg + g) * 2;
                     dst[0] = a;
                     dst[1] = q;
@@ -350,8 +492,8 @@ __device__ __forceinline__ void idb_gemm_epilogue(const GemmParams& p, char* sme
                     // blocked slab: the reduce + GroupNorm-statistics kernel then reads each of its 64 x swc windows as ONE
                     // contiguous run (row-major windows of 40-64 channels are 160-256-byte pieces at a row stride)
                     if (n < p.N) {
-                        const int sl = n / p.slab_swc;
-                        float* blk = p.partial + ((((long long)kz * (p.M >> 6) + (m >> 6)) * (p.N / p.slab_swc) + sl) * 64 + (m & 63)) * p.slab_swc;
+                        const int sl = idb_fd_div(n, p.fd_swc);
+                        float* blk = p.partial + ((((long long)kz * (p.M >> 6) + (m >> 6)) * p.slab_nb + sl) * 64 + (m & 63)) * p.slab_swc;
                         *(f32x4*)(blk + (n - sl * p.slab_swc)) = acc[i][j];
                     }
                 } else if (vec4 && n + 3 < p.N) {
@@ -428,7 +570,7 @@ __device__ __forceinline__ void idb_gemm_epilogue(const GemmParams& p, char* sme
     for (int i = 0; i < MF; ++i) {
         const int m = m0 + (wm * MF + i) * 16 + fr;
         if (m >= p.M) continue;
-        const float* sb = p.sbias ? p.sbias + (long long)(m / p.HW) * p.sbias_ld : nullptr;
+        const float* sb = p.sbias ? p.sbias + (long long)idb_fd_div(m, p.fd_hw) * p.sbias_ld : nullptr;
         if (p.geglu) {
             if constexpr ((NF & 1) == 0) {
 #pragma unroll
@@ -526,15 +668,45 @@ __device__ __forceinline__ void idb_gemm_epilogue(const GemmParams& p, char* sme
 // kernel spent its time in that many dependent round trips.  Slabs are added in ascending split order (deterministic, and
 // bit-identical to the in-kernel reduce).  VEC = 1 is the scalar fallback for odd widths / unaligned residuals.
 // RELU: idb_gemm_desc.act = 3, max(v, 0) after the biases, before the one rounding (its own kernel, idb_splitk_reduce_relu_kernel).
+// Launch geometry of the reduce kernels, resolved on the host like GemmParams': the thread -> (row, column) split and the row's sample
+struct ReduceGeom {
+    idb_fastdiv fd_nv;    // thread index / (N / VEC)                          (plain reduce; exact below 2^31 threads)
+    idb_fastdiv fd_hw;    // m / HW
+    idb_fastdiv fd_cols;  // idb_splitk_reduce_gn_kernel: tid / (swc / 4)
+    idb_fastdiv fd_cpg;   //   channel / group width
+    int cpg, gps;         //   group width N / groups, groups per slice swc / cpg
+    int wide;             // plain reduce: M * N / VEC >= 2^31 threads — the 64-bit division, behind a uniform branch
+};
+
+inline ReduceGeom idb_reduce_geometry(long long M, int n, int hw, int vec, int groups, int swc) {
+    ReduceGeom g = {};
+    g.wide = M * n / vec >= (1LL << 31);
+    g.fd_nv = idb_fastdiv_make((uint32_t)(n / vec > 0 ? n / vec : 1), 0x7FFFFFFFu);
+    g.fd_hw = idb_fastdiv_make((uint32_t)hw, 0x7FFFFFFFu);
+    g.cpg = groups > 0 && n / groups > 0 ? n / groups : 1;
+    g.gps = swc / g.cpg;
+    g.fd_cols = idb_fastdiv_make((uint32_t)(swc >= 4 ? swc >> 2 : 1), 0xFFFFu);
+    g.fd_cpg = idb_fastdiv_make((uint32_t)g.cpg, 0x7FFFFFFFu);
+    return g;
+}
+
 template <typename T, int VEC, bool RELU>
-__device__ __forceinline__ void idb_splitk_reduce_body(const float* __restrict__ partial, int splitk, int M, int N, int HW, float scale,
+__device__ __forceinline__ void idb_splitk_reduce_body(const ReduceGeom geo, const float* __restrict__ partial, int splitk, int M, int N, int HW, float scale,
                                                        const float* bias, const float* sbias, int sbias_ld, const T* res, void* out,
                                                        int out_ld, int out_f32) {
     const long long total = (long long)M * N / VEC;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const long long e0 = idx * VEC;
-    const int m = (int)(e0 / N), n = (int)(e0 - (long long)m * N);
+    int m, n;
+    if (geo.wide) {
+        m = (int)(e0 / N);
+        n = (int)(e0 - (long long)m * N);
+    } else {
+        m = idb_fd_div((int)idx, geo.fd_nv);
+        n = ((int)idx - m * (N / VEC)) * VEC;
+    }
+    const int mb = idb_fd_div(m, geo.fd_hw);            // the row's sample
     if constexpr (VEC == 4) {
         using V4 = typename Op<T>::v4;
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -542,7 +714,7 @@ __device__ __forceinline__ void idb_splitk_reduce_body(const float* __restrict__
         f32x4 bi = zero, sbv = zero;
         if (res) r4 = *(const V4*)(res + (long long)m * out_ld + n);          // uniform conditions: no divergence, and the
         if (bias) bi = *(const f32x4*)(bias + n);                                // waits for these sit behind the slab loads
-        if (sbias) sbv = *(const f32x4*)(sbias + (long long)(m / HW) * sbias_ld + n);
+        if (sbias) sbv = *(const f32x4*)(sbias + (long long)mb * sbias_ld + n);
         const float* src = partial + (long long)m * N + n;
         const long long slab = (long long)M * N;
         f32x4 v = zero;
@@ -576,7 +748,7 @@ __device__ __forceinline__ void idb_splitk_reduce_body(const float* __restrict__
         for (int z = 0; z < splitk; ++z) v += partial[((long long)z * M + m) * N + n];
         v *= scale;
         if (bias) v += bias[n];
-        if (sbias) v += sbias[(long long)(m / HW) * sbias_ld + n];
+        if (sbias) v += sbias[(long long)mb * sbias_ld + n];
         if constexpr (RELU) v = fmaxf(v, 0.f);
         if (res) v += to_f32<T>(res[(long long)m * out_ld + n]);
         if (out_f32) ((float*)out)[(long long)m * out_ld + n] = v;
@@ -585,19 +757,19 @@ __device__ __forceinline__ void idb_splitk_reduce_body(const float* __restrict__
 }
 
 template <typename T, int VEC>
-__global__ __launch_bounds__(256) void idb_splitk_reduce_kernel(const float* __restrict__ partial, int splitk,
+__global__ __launch_bounds__(256) void idb_splitk_reduce_kernel(const ReduceGeom geo, const float* __restrict__ partial, int splitk,
                                                                 int M, int N, int HW, float scale,
                                                                 const float* bias, const float* sbias, int sbias_ld,
                                                                 const T* res, void* out, int out_ld, int out_f32) {
-    idb_splitk_reduce_body<T, VEC, false>(partial, splitk, M, N, HW, scale, bias, sbias, sbias_ld, res, out, out_ld, out_f32);
+    idb_splitk_reduce_body<T, VEC, false>(geo, partial, splitk, M, N, HW, scale, bias, sbias, sbias_ld, res, out, out_ld, out_f32);
 }
 
 template <typename T, int VEC>
-__global__ __launch_bounds__(256) void idb_splitk_reduce_relu_kernel(const float* __restrict__ partial, int splitk,
+__global__ __launch_bounds__(256) void idb_splitk_reduce_relu_kernel(const ReduceGeom geo, const float* __restrict__ partial, int splitk,
                                                                      int M, int N, int HW, float scale,
                                                                      const float* bias, const float* sbias, int sbias_ld,
                                                                      const T* res, void* out, int out_ld, int out_f32) {
-    idb_splitk_reduce_body<T, VEC, true>(partial, splitk, M, N, HW, scale, bias, sbias, sbias_ld, res, out, out_ld, out_f32);
+    idb_splitk_reduce_body<T, VEC, true>(geo, partial, splitk, M, N, HW, scale, bias, sbias, sbias_ld, res, out, out_ld, out_f32);
 }
 
 // Split-K tail that also emits the first GroupNorm pass of its output (idb_gemm_desc.gn_partials): one workgroup owns 64
@@ -608,7 +780,7 @@ __global__ __launch_bounds__(256) void idb_splitk_reduce_relu_kernel(const float
 // 5.5 + 5.4 us (batch 1: +0.7 %).  Measured and dropped: a serial 6-rows-per-thread form (slower than the two launches) and a
 // 2-rows-per-thread form with 80-128-channel slices (longer contiguous runs but half the workgroups: no gain).
 template <typename T>
-__global__ __launch_bounds__(1024) void idb_splitk_reduce_gn_kernel(const float* __restrict__ partial, int splitk, int M, int N,
+__global__ __launch_bounds__(1024) void idb_splitk_reduce_gn_kernel(const ReduceGeom geo, const float* __restrict__ partial, int splitk, int M, int N,
                                                                     int HW, float scale, const float* bias, const float* sbias,
                                                                     int sbias_ld, const T* res, T* out, int out_ld, float* gn_part,
                                                                     int groups, int swc) {
@@ -616,8 +788,7 @@ __global__ __launch_bounds__(1024) void idb_splitk_reduce_gn_kernel(const float*
     __shared__ float part[1024][2][2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cols = swc >> 2;                                  // blockDim.x == 64 * cols
-    const int col = tid % cols, row = tid / cols;
-    const int cpg = N / groups;
+    const int row = idb_fd_div(tid, geo.fd_cols), col = tid - row * cols;
     const int n = blockIdx.y * swc + col * 4;
     const int m_blk = blockIdx.x * 64, m = m_blk + row;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -625,7 +796,7 @@ __global__ __launch_bounds__(1024) void idb_splitk_reduce_gn_kernel(const float*
     f32x4 bi = zero, sbv = zero;
     if (res) r4 = *(const V4*)(res + (long long)m * out_ld + n);
     if (bias) bi = *(const f32x4*)(bias + n);
-    if (sbias) sbv = *(const f32x4*)(sbias + (long long)(m / HW) * sbias_ld + n);
+    if (sbias) sbv = *(const f32x4*)(sbias + (long long)idb_fd_div(m, geo.fd_hw) * sbias_ld + n);
     // slabs in the blocked layout GemmParams::slab_swc describes: this workgroup's window is one contiguous run per slab
     const float* src = partial + (((long long)blockIdx.x * gridDim.y + blockIdx.y) * 64 + row) * swc + col * 4;
     const long long slab = (long long)M * N;
@@ -641,7 +812,7 @@ __global__ __launch_bounds__(1024) void idb_splitk_reduce_gn_kernel(const float*
             for (int e = 0; e < 4; ++e) v[e] += in ? t[u][e] : 0.f;
         }
     }
-    const int g_first = n / cpg;
+    const int g_first = idb_fd_div(n, geo.fd_cpg);
     float gs[2] = {0.f, 0.f}, gq[2] = {0.f, 0.f};
     V4 o;
 #pragma unroll
@@ -652,7 +823,7 @@ __global__ __launch_bounds__(1024) void idb_splitk_reduce_gn_kernel(const float*
         if (res) x += to_f32<T>(r4[e]);
         o[e] = from_f32<T>(x);
         const float xr = to_f32<T>(o[e]);
-        const int k = ((n + e) / cpg - g_first) & 1;            // four channels touch at most two groups (cpg >= 2)
+        const int k = (idb_fd_div(n + e, geo.fd_cpg) - g_first) & 1;            // four channels touch at most two groups (cpg >= 2)
         gs[k] += xr;
         gq[k] += xr * xr;
     }
@@ -660,16 +831,16 @@ __global__ __launch_bounds__(1024) void idb_splitk_reduce_gn_kernel(const float*
     part[tid][0][0] = gs[0]; part[tid][0][1] = gq[0];
     part[tid][1][0] = gs[1]; part[tid][1][1] = gq[1];
     __syncthreads();
-    const int gps = swc / cpg, nact = cols * 64, nwaves = cols;   // 64 * cols threads = cols waves
+    const int gps = geo.gps, nact = cols * 64, nwaves = cols;   // 64 * cols threads = cols waves
     const int slice_g0 = blockIdx.y * gps;
     const int nch = HW >> 6;
-    const int b = m_blk / HW, chunk = (m_blk - b * HW) >> 6;
+    const int b = idb_fd_div(m_blk, geo.fd_hw), chunk = (m_blk - b * HW) >> 6;
     for (int gl = wave; gl < gps; gl += nwaves) {
         const int ga = slice_g0 + gl;
         float a = 0.f, q = 0.f;
         for (int t = lane; t < nact; t += 64) {
-            const int tc = blockIdx.y * swc + (t % cols) * 4;
-            const int k = ga - tc / cpg;
+            const int tc = blockIdx.y * swc + (t - idb_fd_div(t, geo.fd_cols) * cols) * 4;
+            const int k = ga - idb_fd_div(tc, geo.fd_cpg);
             if (k == 0 || k == 1) {
                 a += part[t][k][0];
                 q += part[t][k][1];
@@ -728,7 +899,7 @@ int idb_finish_splitk(const GemmParams& p, int M, int n, int batch, int splitk, 
     if (splitk == 1 || p.counters) return IDB_OK;
     if (p.slab_swc) {
         const int swc = p.slab_swc;       // chosen together with the blocked slab layout the GEMM has just written
-        hipLaunchKernelGGL((idb_splitk_reduce_gn_kernel<T>), dim3(M / 64, n / swc), dim3(16 * swc), 0, st, p.partial, splitk, M, n, p.HW,
+        hipLaunchKernelGGL((idb_splitk_reduce_gn_kernel<T>), dim3(M / 64, n / swc), dim3(16 * swc), 0, st, idb_reduce_geometry(M, n, p.HW, 4, gn_groups, swc), p.partial, splitk, M, n, p.HW,
                            p.scale, p.bias, p.sbias, p.sbias_ld, (const T*)p.res, (T*)p.out, p.out_ld, gn_partials, gn_groups, swc);
         IDB_CHECK_LAUNCH("idb_splitk_reduce_gn");
         return IDB_OK;
@@ -736,21 +907,22 @@ int idb_finish_splitk(const GemmParams& p, int M, int n, int batch, int splitk, 
     const int vec = idb_reduce_vec_ok(p, n) ? 4 : 1;
     const long long total = (long long)M * n / vec;
     const int blocks = (int)((total + 255) / 256);
+    const ReduceGeom geo = idb_reduce_geometry(M, n, p.HW, vec, 0, 0);
     if (relu) {             // act = 3 (the host refuses it with gn_partials, so nothing follows)
         if (vec == 4)
-            hipLaunchKernelGGL((idb_splitk_reduce_relu_kernel<T, 4>), dim3(blocks), dim3(256), 0, st, p.partial, splitk, M, n, p.HW, p.scale,
+            hipLaunchKernelGGL((idb_splitk_reduce_relu_kernel<T, 4>), dim3(blocks), dim3(256), 0, st, geo, p.partial, splitk, M, n, p.HW, p.scale,
                                p.bias, p.sbias, p.sbias_ld, (const T*)p.res, p.out, p.out_ld, p.out_f32);
         else
-            hipLaunchKernelGGL((idb_splitk_reduce_relu_kernel<T, 1>), dim3(blocks), dim3(256), 0, st, p.partial, splitk, M, n, p.HW, p.scale,
+            hipLaunchKernelGGL((idb_splitk_reduce_relu_kernel<T, 1>), dim3(blocks), dim3(256), 0, st, geo, p.partial, splitk, M, n, p.HW, p.scale,
                                p.bias, p.sbias, p.sbias_ld, (const T*)p.res, p.out, p.out_ld, p.out_f32);
         IDB_CHECK_LAUNCH("idb_splitk_reduce_relu");
         return IDB_OK;
     }
     if (vec == 4)
-        hipLaunchKernelGGL((idb_splitk_reduce_kernel<T, 4>), dim3(blocks), dim3(256), 0, st, p.partial, splitk, M, n, p.HW, p.scale, p.bias,
+        hipLaunchKernelGGL((idb_splitk_reduce_kernel<T, 4>), dim3(blocks), dim3(256), 0, st, geo, p.partial, splitk, M, n, p.HW, p.scale, p.bias,
                            p.sbias, p.sbias_ld, (const T*)p.res, p.out, p.out_ld, p.out_f32);
     else
-        hipLaunchKernelGGL((idb_splitk_reduce_kernel<T, 1>), dim3(blocks), dim3(256), 0, st, p.partial, splitk, M, n, p.HW, p.scale, p.bias,
+        hipLaunchKernelGGL((idb_splitk_reduce_kernel<T, 1>), dim3(blocks), dim3(256), 0, st, geo, p.partial, splitk, M, n, p.HW, p.scale, p.bias,
                            p.sbias, p.sbias_ld, (const T*)p.res, p.out, p.out_ld, p.out_f32);
     IDB_CHECK_LAUNCH("idb_splitk_reduce");
     if (gn_partials) return idb_launch_gn_stats64(p.out, n, batch, p.HW, gn_groups, gn_partials, dtype, st);

@@ -23,29 +23,13 @@
     //          tile, so every weight and activation byte crosses the fabric once instead of once per XCD — on the batch-1
     //          weight-streaming layers (M = 512: 4 row tiles on 4 XCD pairs) mode 0 fetched the weights 4-8 times
     //          (rocprofv3 FETCH_SIZE: 99-113 MB per launch against 28-40 MB of operands).
-    int wg, kz;
-    if (p.xcd_mode == 0) {
-        const int nwg = gridDim.x, orig = blockIdx.x;
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-        wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-        kz = blockIdx.z;
-    } else {
-        const int X = gridDim.x;
-        const int lin = blockIdx.x + X * blockIdx.z;
-        const int xcd = lin & 7, j = lin >> 3;
-        if (p.xcd_mode == 1) {
-            kz = xcd + 8 * (j / X);
-            wg = j % X;
-        } else {
-            kz = xcd >> 1;
-            wg = (xcd & 1) * (X >> 1) + j;
-        }
-    }
-    const int tm = wg / p.tiles_n, tn = wg - tm * p.tiles_n;
+    int wg, kz, tm, tn;
+    idb_wg_tile(p, wg, kz);
+    idb_tile_mn(p, wg, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
 
-    const int kt0 = (int)(((long long)kz * p.ktiles) / p.splitk);          // balanced partition: slice sizes differ by at most one
-    const int kt1 = (int)(((long long)(kz + 1) * p.ktiles) / p.splitk);
+    int kt0, kt1;                                            // balanced partition: slice sizes differ by at most one
+    idb_k_range(p, kz, kt0, kt1);
     const int nk = kt1 - kt0;
 
     // ---- per-thread staging coordinates: thread loads chunk position (tid&7) of rows (tid>>3)+32i;
@@ -58,16 +42,7 @@
     for (int i = 0; i < MF; ++i) {
         const int m = m0 + i * RS + lrow;
         a_ok[i] = m < p.M;
-        const int mm = a_ok[i] ? m : 0;
-        if (p.HW == 1) {                     // plain [M][K] matrix: no pixel decode (two integer divisions per row)
-            a_b[i] = mm;
-            a_oy[i] = a_ox[i] = 0;
-        } else {
-            a_b[i] = mm / p.HW;
-            const int rem = mm - a_b[i] * p.HW;
-            a_oy[i] = rem / p.OW;
-            a_ox[i] = rem - a_oy[i] * p.OW;
-        }
+        idb_row_decode(p, a_ok[i] ? m : 0, a_b[i], a_oy[i], a_ox[i]);
     }
     // weights: one descriptor, per-row voffset fixed for the whole K loop, K position in the SGPR soffset
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w + idb_weight_group(p, m0) * p.w_group_stride), 0, p.w_bytes, IDB_RSRC_FLAGS);
@@ -83,24 +58,8 @@
     // Per-row voffsets (pixel address, zero padding -> out-of-range) are recomputed only when the tap or the
     // source changes (every C/64 K-steps); inside a tap the channel offset rides in the SGPR soffset, so a
     // K-step costs no address VALU at all.
-    int s = 0, tap = 0, c0 = 0, cur_c = 64, tap_end = 9;
-    {
-        int rem = kt0;
-        while (s < IDB_MAX_SRC - 1) {
-            const int steps = p.src[s].taps * (p.src[s].C >> 6);
-            if (rem < steps) break;
-            rem -= steps;
-            ++s;
-        }
-        const int cs = p.src[s].C >> 6;
-        if (p.src[s].taps == 9) {
-            tap = rem / cs;
-            c0 = (rem - tap * cs) << 6;
-        } else {
-            tap = 4;
-            c0 = rem << 6;
-        }
-    }
+    int s, tap, c0, cur_c = 64, tap_end = 9;
+    idb_k_seek(p, kt0, s, tap, c0);
     __amdgpu_buffer_rsrc_t rs_a = rs_w;
     unsigned a_voff[MF];
     bool need_retap = true;
