@@ -17,6 +17,7 @@ IDB_BF16, IDB_F16, IDB_F32 = 0, 1, 2
 IDB_MAX_SRC = 4
 IDB_PLMS_SLOTS = 4
 IDB_PLMS_KEEP, IDB_PLMS_SAVE, IDB_PLMS_RESTORE = 0, 1, 2
+IDB_HEAD_COSFACE, IDB_HEAD_ARCFACE, IDB_HEAD_ADAFACE = 0, 1, 2
 IDB_PAIR_DIST2, IDB_PAIR_KNN, IDB_PAIR_PRDC, IDB_PAIR_NEAREST, IDB_PAIR_POLY = 0, 1, 2, 3, 4
 # the selected points of idb_verif_roc, in the order of its points / ints outputs
 IDB_VERIF_POINTS = ("eer_t2", "eer_t1", "fmr0", "fmr1000", "fmr100", "fmr20", "fmr10", "fnmr0", "fnmr100", "fnmr1000", "youden", "mcc", "first")
@@ -43,6 +44,7 @@ EXPORTS = [
     "idb_diffuse_targets", "idb_objective_workspace_bytes", "idb_objective_mse_x0", "idb_crop_resize_bilinear_f32", "idb_crop_resize_area_f32",
     "idb_identity_losses",
     "idb_randaug",
+    "idb_head_pack", "idb_head_workspace_bytes", "idb_head_loss", "idb_head_logits",
 ]
 
 
@@ -74,6 +76,13 @@ class GemmFp8Desc(C.Structure):
                 ("in_w", C.c_int32), ("upsample", C.c_int32), ("x_scale", C.c_float), ("w", C.c_void_p), ("w_scale", C.c_void_p),
                 ("bias", C.c_void_p), ("sample_bias", C.c_void_p), ("sample_bias_ld", C.c_int32), ("residual", C.c_void_p),
                 ("out", C.c_void_p), ("out_ld", C.c_int32), ("gn_partials", C.c_void_p), ("gn_groups", C.c_int32)]
+
+
+class HeadDesc(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("b", C.c_int32), ("d", C.c_int32), ("c", C.c_int32),
+                ("s", C.c_double), ("m", C.c_double), ("h", C.c_double), ("t_alpha", C.c_double),
+                ("emb", C.c_void_p), ("norms", C.c_void_p), ("label", C.c_void_p), ("kernel", C.c_void_p),
+                ("wn", C.c_void_p), ("col_norm", C.c_void_p), ("ada_state", C.c_void_p)]
 
 
 class IdbError(RuntimeError):
@@ -176,6 +185,10 @@ def load() -> C.CDLL:
         "idb_crop_resize_area_f32": (C.c_int, [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, f32, f32, vp]),
         "idb_identity_losses": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp]),
         "idb_randaug": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
+        "idb_head_pack": (C.c_int, [vp, i32, i32, vp, vp, vp, vp]),
+        "idb_head_workspace_bytes": (sz, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
+        "idb_head_loss": (C.c_int, [C.POINTER(HeadDesc), vp, vp, vp, vp, vp, sz, vp]),
+        "idb_head_logits": (C.c_int, [C.POINTER(HeadDesc), vp, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

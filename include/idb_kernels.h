@@ -693,6 +693,58 @@ int idb_identity_losses(const float* feat, const float* pos, const float* neg, i
 int idb_randaug(const uint8_t* in, int32_t n, int32_t h, int32_t w, const uint8_t* flip, const int32_t* slot_op, const int32_t* slot_iarg,
                 const float* slot_farg, int32_t num_ops, uint8_t* out_u8, float* out_f32_nchw, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The FR-training loss head (ID-Booth's FR_training/utils/losses.py: CosFace :58-81, ArcFace :32-55, AdaFace :126-204, then
+ * train_FR.py:288 CrossEntropyLoss and :302 / :373-377 multi_class_acc), forward only, fp32 operands on the exact f32-input MFMA.
+ * Every entry validates its arguments before any HIP call, uses fixed-order sums and no floating-point atomics (bit-identical from
+ * run to run) and never synchronises.
+ *   idb_head_pack: replaces `l2_norm(self.kernel, axis=0)` (losses.py:26-29, :44 / :70 / :161, recomputed upstream on every call).
+ *       kernel: fp32 [d][c] row-major, as torch stores the parameter.  wn: fp32 [c][d], column j of kernel divided by its norm (the
+ *       norm summed in double, one division, one rounding).  col_norm: double [c].  bad_cols: int32 [1] device, the number of columns
+ *       whose norm is zero or not finite (upstream gives NaN logits for them; the caller refuses).  1 <= d <= 4096, 1 <= c <= 2^20.
+ *   idb_head_workspace_bytes(b, d, c, row_tiles, col_blocks): the workspace of idb_head_loss / idb_head_logits, 0 for shapes they
+ *       refuse; row_tiles / col_blocks (either may be NULL) receive the loss kernel's grid: tiles of 128 rows, and the blocks of
+ *       columns whose partial log-sum-exp, maximum and argmax are merged in ascending order.
+ *   idb_head_loss: replaces the header's forward, `criterion(thetas, labels)` and `multi_class_acc(thetas, labels)` without writing
+ *       the b x c matrix.  Launches: (AdaFace: batch statistics,) per-row prep, loss tiles, merge, mean.
+ *       Per row i: n_i = |emb_i| and x_i = emb_i / n_i (double, rounded once; AdaFace takes emb as it is, as upstream), the target
+ *       cosine c_i = <emb_i, kernel[:, label_i]> / (n_i col_norm[label_i]) in double, and the target logit in double:
+ *         CosFace  s (clamp(c, -1, 1) - m)                         ArcFace  s cos(acos(clamp(c, -1, 1)) + m)
+ *         AdaFace  e = 1e-3, safe = clip(norms, 0.001, 100), mean / std = its batch mean / unbiased std, ada_state[0 / 1] <-
+ *                  mean (std) t_alpha + (1 - t_alpha) ada_state[0 / 1] (updated in place on every call, as upstream),
+ *                  scaler = clip((safe - ada_state[0]) / (ada_state[1] + e) h, -1, 1),
+ *                  s (cos(clip(acos(clamp(c, -1 + e, 1 - e)) - m scaler, e, pi - e)) - (m + m scaler)).
+ *       Every other logit is fp32 s * clamp(<x_i, wn_j>, -1, 1) (AdaFace: -1 + e, 1 - e, on every entry); column label_i is REPLACED
+ *       by the fp32 rounding of the target logit.  rows: double [5][b]: log-sum-exp, loss_i = lse - target logit, target logit,
+ *       target cosine (before the clamp), AdaFace's margin scaler (else 0).  pred: int32 [b], the argmax, the lowest column among
+ *       equal logits (torch.argmax).  mean_loss: double [1], the rows' losses summed in a fixed order / b.  correct: int32 [1],
+ *       #{pred == label}.  A label outside [0, c) reads nothing and gives that row NaN (callers refuse it: upstream's
+ *       CrossEntropyLoss raises).  1 <= b <= 65536 (AdaFace: b >= 2), d and c as above; s in (0, 1e4]; t_alpha in [0, 1];
+ *       wn == NULL (an unpacked header) is IDB_EINVAL.  ws 16-byte aligned.
+ *   idb_head_logits: the `thetas` [b][c] fp32 the header returns upstream (API parity and per-element tests; not on the loss path):
+ *       (statistics,) prep, one tile launch with a store epilogue.  rows as above; its first two planes are left untouched.
+ * ------------------------------------------------------------------------------------------ */
+#define IDB_HEAD_COSFACE 0
+#define IDB_HEAD_ARCFACE 1
+#define IDB_HEAD_ADAFACE 2
+typedef struct idb_head_desc {
+    int32_t kind;            /* IDB_HEAD_* */
+    int32_t b, d, c;
+    double s, m, h, t_alpha; /* h, t_alpha: AdaFace */
+    const float* emb;        /* [b][d] */
+    const float* norms;      /* [b], AdaFace (else NULL) */
+    const int32_t* label;    /* [b] */
+    const float* kernel;     /* [d][c], the header's parameter */
+    const float* wn;         /* [c][d], idb_head_pack */
+    const double* col_norm;  /* [c], idb_head_pack */
+    double* ada_state;       /* [2] batch_mean, batch_std: read and updated (AdaFace, else NULL) */
+} idb_head_desc;
+int idb_head_pack(const float* kernel, int32_t d, int32_t c, float* wn, double* col_norm, int32_t* bad_cols, void* stream);
+size_t idb_head_workspace_bytes(int32_t b, int32_t d, int32_t c, int32_t* row_tiles, int32_t* col_blocks);
+int idb_head_loss(const idb_head_desc* h, double* rows, int32_t* pred, double* mean_loss, int32_t* correct, void* ws, size_t ws_bytes,
+                  void* stream);
+int idb_head_logits(const idb_head_desc* h, float* thetas, double* rows, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
