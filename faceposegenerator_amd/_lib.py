@@ -18,6 +18,7 @@ IDB_MAX_SRC = 4
 IDB_PLMS_SLOTS = 4
 IDB_PLMS_KEEP, IDB_PLMS_SAVE, IDB_PLMS_RESTORE = 0, 1, 2
 IDB_HEAD_COSFACE, IDB_HEAD_ARCFACE, IDB_HEAD_ADAFACE = 0, 1, 2
+IDB_HEAD_SGD_WS_BYTES = 8192
 IDB_PAIR_DIST2, IDB_PAIR_KNN, IDB_PAIR_PRDC, IDB_PAIR_NEAREST, IDB_PAIR_POLY = 0, 1, 2, 3, 4
 # the selected points of idb_verif_roc, in the order of its points / ints outputs
 IDB_VERIF_POINTS = ("eer_t2", "eer_t1", "fmr0", "fmr1000", "fmr100", "fmr20", "fmr10", "fnmr0", "fnmr100", "fnmr1000", "youden", "mcc", "first")
@@ -45,6 +46,7 @@ EXPORTS = [
     "idb_identity_losses",
     "idb_randaug",
     "idb_head_pack", "idb_head_workspace_bytes", "idb_head_loss", "idb_head_logits",
+    "idb_head_grad_workspace_bytes", "idb_head_loss_grad", "idb_head_sgd_step",
 ]
 
 
@@ -189,6 +191,10 @@ def load() -> C.CDLL:
         "idb_head_workspace_bytes": (sz, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "idb_head_loss": (C.c_int, [C.POINTER(HeadDesc), vp, vp, vp, vp, vp, sz, vp]),
         "idb_head_logits": (C.c_int, [C.POINTER(HeadDesc), vp, vp, vp, sz, vp]),
+        "idb_head_grad_workspace_bytes": (sz, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "idb_head_loss_grad": (C.c_int, [C.POINTER(HeadDesc), vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "idb_head_sgd_step": (C.c_int, [vp, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, i32, vp, vp, vp, vp, vp, sz,
+                                        vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

@@ -12,6 +12,11 @@
 //   merge  up to a wave of lanes per row take its column blocks in ascending order and meet in a fixed butterfly
 //   mean   one block: the mean loss as a fixed-order double sum and the count of correct rows
 //   logits the same tile loop with the operands the usual way round (a lane owns a class, stores are coalesced) and a store epilogue
+//   grad   the backward (idb_head_loss_grad): the cosine tile is recomputed on the MFMA, G = (softmax - one-hot) s d mask / B is formed
+//          in the accumulator registers from the forward's log-sum-exp, and the accumulator tile is the A operand of the second product
+//          as it stands (its column is on the lane, its rows are the reduction index): dX = G Wn per (row tile, class block) with the
+//          blocks merged in ascending order, dW = G^T X per class tile over all row tiles, projected and written as kernel.grad
+//   sgd    clip_grad_norm_ and SGD with momentum on the kernel: squared-sum partials, then the step (idb_head_sgd_step), then pack
 // No floating-point atomics, every sum in a fixed order that depends on the shapes alone: results are bit-identical from run to run.
 #include "idb_common.h"
 #include <math.h>
@@ -386,6 +391,270 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const float* __restric
         }
 }
 
+// ---- backward ---------------------------------------------------------------------------------------------------------------------
+constexpr int GK = 4;                  // 32-column chunks of D per gradient workgroup: 128 columns, 4 accumulator tiles per wave
+constexpr int GRAD_WGS = 256;          // class blocks x row tiles of the dX launch stays near this: bounds its partials
+constexpr long long GRAD_MAX_PART = 1LL << 27;     // floats of dX partials (blocks x B x D) the backward accepts: 512 MiB
+
+// grad_rows [3][B] double: [0] the target's slope d_i = dz_t / (s dr_t) with the clamp (and AdaFace's clip) folded in: 0 where the
+// target is clamped away, [1] that mask, [2] |e_i| (AdaFace: 1, its rows are taken as they are).  From the double target cosine and
+// margin scaler the forward's prep left in rows[3], rows[4]; the norm is summed in the order the prep sums it.
+__global__ __launch_bounds__(256) void head_grad_prep_kernel(const float* __restrict__ emb, const double* __restrict__ rows, int B, int D,
+                                                             HeadMargin mg, double* __restrict__ grad_rows) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+    if (i >= B) return;
+    double uu = 0.0;
+    if (mg.kind != IDB_HEAD_ADAFACE) {
+        const float* e = emb + (long long)i * D;
+        for (int k = l; k < D; k += 64) {
+            const double x = (double)e[k];
+            uu += x * x;
+        }
+        uu = wave_sum_d(uu);
+    }
+    if (l != 0) return;
+    const double c = rows[3LL * B + i];
+    double slope, mask;
+    if (mg.kind == IDB_HEAD_COSFACE) {
+        mask = c >= -1.0 && c <= 1.0 ? 1.0 : 0.0;      // inclusive, as torch's clamp backward; a NaN gives 0
+        slope = mask;
+    } else if (mg.kind == IDB_HEAD_ARCFACE) {
+        mask = c >= -1.0 && c <= 1.0 ? 1.0 : 0.0;
+        slope = mask != 0.0 ? sin(acos(c) + mg.m) / sqrt(1.0 - c * c) : 0.0;       // c = +-1 exactly: not finite, the caller refuses
+    } else {
+        mask = c >= -1.0 + ADA_EPS && c <= 1.0 - ADA_EPS ? 1.0 : 0.0;
+        const double cc = clampd(c, -1.0 + ADA_EPS, 1.0 - ADA_EPS);
+        const double theta = acos(cc) + mg.m * rows[4LL * B + i] * -1.0;
+        slope = mask != 0.0 && theta >= ADA_EPS && theta <= M_PI - ADA_EPS ? sin(theta) / sqrt(1.0 - cc * cc) : 0.0;
+    }
+    grad_rows[i] = slope;
+    grad_rows[(long long)B + i] = mask;
+    grad_rows[2LL * B + i] = mg.kind == IDB_HEAD_ADAFACE ? 1.0 : sqrt(uu);
+}
+
+// Both gradient products.  A lane owns one row of P and meets, in its 64 accumulator registers, 64 of the 128 rows of each tile of Q:
+//   DW = false (dX = G Wn):   P = the embeddings, Q = Wn; grid (class blocks, row tiles, D chunks); class block b takes class tiles
+//                             b per .. of 128 and writes its partial dX rows and <x_i, dX_i> = sum_j G_ij r_ij to the workspace
+//   DW = true  (dW = G^T X):  P = Wn, Q = the embeddings; grid (class tiles of 128, 1, D chunks); a workgroup takes every row tile in
+//                             ascending order, so it holds the finished dW_j and <w_j, dW_j> = sum_i G_ij r_ij, projects and writes
+//                             kernel.grad [D][C] (transposed through LDS: stores coalesced along C)
+// The cosine tile acc[t][e] = <Q[m0 + tile_row(t, e, h)], P[lane's row]> is turned into G in place; it then is the A operand of
+// out[p][k] += sum_q G[p][q] Q[q][k] with no lane movement: MFMA step (t, e) reduces over q = tile_row(t, e, h), h the half-wave,
+// and reads Q[q][k] from the LDS stage as B.  A wave holds the accumulators of one chunk of 128 columns of D.
+//   MULTI = false: the workgroup owns chunk blockIdx.z and keeps its accumulators in registers across its tiles of Q (D <= 128, where
+//                  there is one chunk; and dW over several row tiles, where every chunk's workgroup recomputes the cosines)
+//   MULTI = true:  the workgroup walks all chunks after each cosine tile, so the cosines are computed once.  dX: a chunk's accumulators
+//                  are reloaded from the block's own partial, which the same lanes stored at the previous tile: the fma chain is the
+//                  one a register-resident accumulator would run.  dW: chosen only where one row tile holds the whole batch.
+template <bool DW, bool MULTI>
+__global__ __launch_bounds__(256) void head_grad_kernel(const float* __restrict__ x, const float* __restrict__ wn, const int32_t* __restrict__ label,
+                                                        const double* __restrict__ rows, const double* __restrict__ grad_rows, int B, int D,
+                                                        int C, int vec, float lo, float hi, float s, double s_over_b, int per,
+                                                        float* __restrict__ part, double* __restrict__ part_dot,
+                                                        const float* __restrict__ kernel, const double* __restrict__ col_norm,
+                                                        float* __restrict__ d_kernel) {
+    __shared__ float sA[HB * HLD], sB[HB * HLD];
+    __shared__ double sLse[HB];
+    __shared__ float sGt[HB];
+    __shared__ int sLab[HB];
+    const float* Q = DW ? x : wn;
+    const float* P = DW ? wn : x;
+    const int nq = DW ? B : C, np = DW ? C : B;
+    const int n0 = (DW ? blockIdx.x : blockIdx.y) * HB;
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6, h = l >> 5, r = l & 31, pj = n0 + w * 32 + r;
+    const int tiles = (nq + HB - 1) / HB, chunks = (D + 32 * GK - 1) / (32 * GK);
+    const int t0 = DW ? 0 : blockIdx.x * per, t1 = DW ? tiles : (t0 + per < tiles ? t0 + per : tiles);
+    const int c0 = MULTI ? 0 : blockIdx.z, c1 = MULTI ? chunks : blockIdx.z + 1;
+    const float s_over_b_f = (float)s_over_b;
+    // the target's entry of G, per row: (p_t - 1) s d_t / B in double, p_t from the fp32 rounding of the target logit that the forward's
+    // log-sum-exp saw (so the row's softmax sums to 1, and a single class gives exactly 0)
+    int lab = -1;
+    double lse = 0.0;
+    float gt = 0.f;
+    if (!DW && pj < B) {
+        lab = label[pj];
+        lse = rows[pj];
+        gt = (float)((exp((double)(float)rows[2LL * B + pj] - lse) - 1.0) * s_over_b * grad_rows[pj]);
+    }
+    const double cn = DW && pj < C ? col_norm[pj] : 1.0;
+    f32x16 out[GK];
+#pragma unroll
+    for (int kc = 0; kc < GK; ++kc)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) out[kc][e] = 0.f;
+    double dot = 0.0;
+
+    // dX: the chunk's rows of this block's partial.  LOAD = false stores them, LOAD = true takes them back (zero where nothing is stored)
+    auto partial = [&](int kbase, bool load) {
+#pragma unroll
+        for (int kc = 0; kc < GK; ++kc)
+            if (kbase + 32 * kc < D) {
+                const int k = kbase + 32 * kc + r;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int p = n0 + w * 32 + tile_row(0, e, h);
+                    const long long o = ((long long)blockIdx.x * B + p) * D + k;
+                    if (load) out[kc][e] = p < B && k < D ? part[o] : 0.f;
+                    else if (p < B && k < D) part[o] = out[kc][e];
+                }
+            }
+    };
+    // dW: the chunk's finished sums, projected, divided and written as kernel.grad [D][C], transposed through LDS
+    auto project = [&](int kbase, double total) {
+#pragma unroll
+        for (int kc = 0; kc < GK; ++kc)
+            if (kbase + 32 * kc < D) {
+                __syncthreads();                           // the previous transpose has been read
+#pragma unroll
+                for (int e = 0; e < 16; ++e) sB[(w * 32 + r) * HLD + tile_row(0, e, h)] = out[kc][e];     // [k][class]
+                __syncthreads();
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int k = kbase + 32 * kc + h * 16 + e;
+                    if (pj < C && k < D) {
+                        const long long o = (long long)k * C + pj;
+                        const double wv = (double)kernel[o] / cn;
+                        d_kernel[o] = (float)(((double)sB[(w * 32 + h * 16 + e) * HLD + r] - wv * total) / cn);
+                    }
+                }
+            }
+    };
+
+    for (int tile = t0; tile < t1; ++tile) {
+        const int m0 = tile * HB;
+        if (DW && threadIdx.x < HB) {                      // published by head_tile's barriers; the last readers passed the barriers below
+            const int i = m0 + threadIdx.x;
+            const bool ok = i < B;
+            sLab[threadIdx.x] = ok ? label[i] : -1;
+            sLse[threadIdx.x] = ok ? rows[i] : 0.0;
+            sGt[threadIdx.x] = ok ? (float)((exp((double)(float)rows[2LL * B + i] - rows[i]) - 1.0) * s_over_b * grad_rows[i]) : 0.f;
+        }
+        f32x16 acc[4];
+        head_tile<4>(Q, nq, P, np, D, vec != 0, m0, n0, sA, sB, acc);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int ql = tile_row(t, e, h), qi = m0 + ql;
+                const int cls = DW ? pj : qi, row = DW ? qi : pj;
+                const float rr = acc[t][e];
+                float g = 0.f;
+                if (cls < C && row < B) {
+                    const int rlab = DW ? sLab[ql] : lab;
+                    const double rlse = DW ? sLse[ql] : lse;
+                    const float z = s * clampf(rr, lo, hi);
+                    const float p = expf((float)((double)z - rlse));
+                    g = rr >= lo && rr <= hi ? p * s_over_b_f : 0.f;
+                    g = cls == rlab ? (DW ? sGt[ql] : gt) : g;
+                }
+                dot += (double)g * (double)rr;
+                acc[t][e] = g;
+                if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);       // four expf chains in flight, not sixty-four: registers
+            }
+        const float* rq[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int qr = (threadIdx.x >> 3) + 32 * i;
+            rq[i] = m0 + qr < nq ? Q + (long long)(m0 + qr) * D : nullptr;
+        }
+        for (int c = c0; c < c1; ++c) {
+            const int kbase = c * 32 * GK;
+            if (MULTI) {
+                if (!DW && tile > t0) partial(kbase, true);
+                else {
+#pragma unroll
+                    for (int kc = 0; kc < GK; ++kc)
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) out[kc][e] = 0.f;
+                }
+            }
+#pragma unroll
+            for (int kc = 0; kc < GK; ++kc)
+                if (kbase + 32 * kc < D) {                 // uniform
+                    f32x4 v[4];
+                    head_fetch<4>(rq, D, vec != 0, kbase + 32 * kc, v);
+                    __syncthreads();                       // the previous stage has been read
+                    head_stash<4>(sA, v);
+                    __syncthreads();
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+#pragma unroll
+                        for (int e = 0; e < 16; ++e)
+                            out[kc] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[t][e], sA[tile_row(t, e, h) * HLD + r], out[kc], 0, 0, 0);
+                }
+            if (MULTI) {
+                if (DW) {                                  // the one row tile: the column's sum over the batch is complete
+                    const double other = __shfl_xor(dot, 32, 64);
+                    project(kbase, h == 0 ? dot + other : other + dot);
+                } else {
+                    partial(kbase, false);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // the two half-waves of a row of P: the lower half's term first
+    const double other = __shfl_xor(dot, 32, 64);
+    const double total = h == 0 ? dot + other : other + dot;
+    if (!DW) {
+        if (!MULTI) partial(c0 * 32 * GK, false);
+        if (blockIdx.z == 0 && h == 0 && pj < B) part_dot[(long long)blockIdx.x * B + pj] = total;
+    } else if (!MULTI) {
+        project(c0 * 32 * GK, total);
+    }
+}
+
+// One workgroup per embedding row: the class blocks' partials in ascending order (double), then the projection onto the tangent of
+// the unit sphere and the division by |e_i|, one rounding.  AdaFace's rows are taken as they are: dX_i is the gradient.
+__global__ __launch_bounds__(256) void head_grad_rows_kernel(const float* __restrict__ part, const double* __restrict__ part_dot,
+                                                             const float* __restrict__ emb, const double* __restrict__ grad_rows, int blocks,
+                                                             int B, int D, int ada, float* __restrict__ d_emb) {
+    const int i = blockIdx.x;
+    double rd = 0.0;
+    for (int b = 0; b < blocks; ++b) rd += part_dot[(long long)b * B + i];
+    const double n = grad_rows[2LL * B + i];
+    for (int k = threadIdx.x; k < D; k += 256) {
+        double acc = 0.0;
+        for (int b = 0; b < blocks; ++b) acc += (double)part[((long long)b * B + i) * D + k];
+        const long long o = (long long)i * D + k;
+        d_emb[o] = ada ? (float)acc : (float)((acc - (double)emb[o] / n * rd) / n);
+    }
+}
+
+// ---- clip_grad_norm_ and SGD ------------------------------------------------------------------------------------------------------
+constexpr int SGD_PARTS = 1024;
+
+// workgroup b sums the squares of elements 256 b + t + 256 gridDim.x i in order, then the fixed block sum
+__global__ __launch_bounds__(256) void head_sqsum_kernel(const float* __restrict__ g, long long n, double* __restrict__ parts) {
+    __shared__ double lds4[4];
+    double s = 0.0;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += gridDim.x * 256LL) {
+        const double v = (double)g[i];
+        s += v * v;
+    }
+    s = block_sum_d(s, lds4);
+    if (threadIdx.x == 0) parts[blockIdx.x] = s;
+}
+
+// every workgroup adds the partials in the same fixed order; the step itself is evaluated in double per element and each fp32 state
+// (the momentum buffer, the weight) is rounded once
+__global__ __launch_bounds__(256) void head_sgd_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ buf, long long n,
+                                                       const double* __restrict__ parts, int nparts, double lr, double momentum, double wd,
+                                                       double max_norm, int first, double* __restrict__ total_norm) {
+    __shared__ double lds4[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 256) s += parts[i];
+    const double norm = sqrt(block_sum_d(s, lds4));
+    const double q = max_norm / (norm + 1e-6), coef = q < 1.0 ? q : 1.0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *total_norm = norm;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += gridDim.x * 256LL) {
+        const double d = coef * (double)g[i] + wd * (double)w[i];
+        const float b = (float)(first ? d : momentum * (double)buf[i] + d);
+        buf[i] = b;
+        w[i] = (float)((double)w[i] - lr * (double)b);
+    }
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------------------
 inline size_t head_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -449,6 +718,59 @@ int head_prep(const char* api, const idb_head_desc* h, const HeadPlan& p, char* 
     return IDB_OK;
 }
 
+// the launches of idb_head_loss, after its checks
+int head_loss_run(const idb_head_desc* h, double* rows, int32_t* pred, double* mean_loss, int32_t* correct, char* w, hipStream_t st) {
+    const HeadPlan p = head_plan(h->b, h->d, h->c);
+    const int rc = head_prep("idb_head_loss(prep)", h, p, w, rows, st);
+    if (rc != IDB_OK) return rc;
+    const bool ada = h->kind == IDB_HEAD_ADAFACE;
+    const float* x = ada ? h->emb : (const float*)(w + p.en);
+    const float lo = ada ? (float)(-1.0 + ADA_EPS) : -1.f, hi = ada ? (float)(1.0 - ADA_EPS) : 1.f;
+    const int vec = h->d % 4 == 0 && idb_aligned16(x) && idb_aligned16(h->wn);
+    const dim3 grid(p.col_blocks, p.row_tiles);
+#define HEAD_LOSS(TA)                                                                                                                   \
+    hipLaunchKernelGGL(head_loss_kernel<TA>, grid, dim3(256), 0, st, x, h->wn, h->label, (const float*)(w + p.zt), h->b, h->d, h->c, vec, lo, \
+                       hi, (float)h->s, p.per, (float*)(w + p.m), (double*)(w + p.s), (int32_t*)(w + p.a))
+    if (p.ta == 4) HEAD_LOSS(4);
+    else if (p.ta == 2) HEAD_LOSS(2);
+    else HEAD_LOSS(1);
+#undef HEAD_LOSS
+    IDB_CHECK_LAUNCH("idb_head_loss");
+    int lanes = 1;                                     // lanes that share a row in the merge: the column blocks, up to a wave
+    while (lanes < 64 && lanes < p.col_blocks) lanes <<= 1;
+    const int rows_per_wg = MERGE_THREADS / lanes;
+    hipLaunchKernelGGL(head_merge_kernel, dim3((h->b + rows_per_wg - 1) / rows_per_wg), dim3(MERGE_THREADS), 0, st, (const float*)(w + p.m),
+                       (const double*)(w + p.s), (const int32_t*)(w + p.a), p.col_blocks, h->b, lanes, rows, pred);
+    IDB_CHECK_LAUNCH("idb_head_loss(merge)");
+    hipLaunchKernelGGL(head_mean_kernel, dim3(1), dim3(256), 0, st, (const double*)rows, (const int32_t*)pred, h->label, h->b, mean_loss,
+                       correct);
+    IDB_CHECK_LAUNCH("idb_head_loss(mean)");
+    return IDB_OK;
+}
+
+struct HeadGradPlan {
+    int row_tiles, per, blocks, chunks;                // the dX launch's grid is (blocks, row_tiles), the dW launch's (class tiles, 1, 1 or chunks)
+    size_t part, dot, total;                           // workspace offsets, after the forward's
+    bool ok;                                           // the dX partials fit GRAD_MAX_PART
+};
+
+// Class blocks of the dX launch: about GRAD_WGS workgroups per D chunk (B = 128, C = 10 572: 83 blocks of one 128-class tile), so
+// the partials are blocks x B x D floats, 64 MiB at B = 1024, C = 2^17, D = 512.
+HeadGradPlan head_grad_plan(int b, int d, int c) {
+    HeadGradPlan g;
+    g.row_tiles = (b + HB - 1) / HB;
+    const int tiles = (c + HB - 1) / HB, cap = GRAD_WGS / g.row_tiles > 1 ? GRAD_WGS / g.row_tiles : 1;
+    g.per = (tiles + cap - 1) / cap;
+    g.blocks = (tiles + g.per - 1) / g.per;
+    g.chunks = (d + 32 * GK - 1) / (32 * GK);
+    g.ok = (long long)g.blocks * b * d <= GRAD_MAX_PART;
+    size_t o = head_plan(b, d, c).total;
+    g.part = o, o += head_align(sizeof(float) * (size_t)g.blocks * b * d);
+    g.dot = o, o += head_align(sizeof(double) * (size_t)g.blocks * b);
+    g.total = o;
+    return g;
+}
+
 }  // namespace
 
 extern "C" int idb_head_pack(const float* kernel, int32_t d, int32_t c, float* wn, double* col_norm, int32_t* bad_cols, void* stream) {
@@ -477,34 +799,7 @@ extern "C" int idb_head_loss(const idb_head_desc* h, double* rows, int32_t* pred
     const int rc0 = head_check("idb_head_loss", h, ws, ws_bytes);
     if (rc0 != IDB_OK) return rc0;
     IDB_REQUIRE(rows && pred && mean_loss && correct, "idb_head_loss: null output pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const HeadPlan p = head_plan(h->b, h->d, h->c);
-    char* w = (char*)ws;
-    const int rc = head_prep("idb_head_loss(prep)", h, p, w, rows, st);
-    if (rc != IDB_OK) return rc;
-    const bool ada = h->kind == IDB_HEAD_ADAFACE;
-    const float* x = ada ? h->emb : (const float*)(w + p.en);
-    const float lo = ada ? (float)(-1.0 + ADA_EPS) : -1.f, hi = ada ? (float)(1.0 - ADA_EPS) : 1.f;
-    const int vec = h->d % 4 == 0 && idb_aligned16(x) && idb_aligned16(h->wn);
-    const dim3 grid(p.col_blocks, p.row_tiles);
-#define HEAD_LOSS(TA)                                                                                                                   \
-    hipLaunchKernelGGL(head_loss_kernel<TA>, grid, dim3(256), 0, st, x, h->wn, h->label, (const float*)(w + p.zt), h->b, h->d, h->c, vec, lo, \
-                       hi, (float)h->s, p.per, (float*)(w + p.m), (double*)(w + p.s), (int32_t*)(w + p.a))
-    if (p.ta == 4) HEAD_LOSS(4);
-    else if (p.ta == 2) HEAD_LOSS(2);
-    else HEAD_LOSS(1);
-#undef HEAD_LOSS
-    IDB_CHECK_LAUNCH("idb_head_loss");
-    int lanes = 1;                                     // lanes that share a row in the merge: the column blocks, up to a wave
-    while (lanes < 64 && lanes < p.col_blocks) lanes <<= 1;
-    const int rows_per_wg = MERGE_THREADS / lanes;
-    hipLaunchKernelGGL(head_merge_kernel, dim3((h->b + rows_per_wg - 1) / rows_per_wg), dim3(MERGE_THREADS), 0, st, (const float*)(w + p.m),
-                       (const double*)(w + p.s), (const int32_t*)(w + p.a), p.col_blocks, h->b, lanes, rows, pred);
-    IDB_CHECK_LAUNCH("idb_head_loss(merge)");
-    hipLaunchKernelGGL(head_mean_kernel, dim3(1), dim3(256), 0, st, (const double*)rows, (const int32_t*)pred, h->label, h->b, mean_loss,
-                       correct);
-    IDB_CHECK_LAUNCH("idb_head_loss(mean)");
-    return IDB_OK;
+    return head_loss_run(h, rows, pred, mean_loss, correct, (char*)ws, (hipStream_t)stream);
 }
 
 extern "C" int idb_head_logits(const idb_head_desc* h, float* thetas, double* rows, void* ws, size_t ws_bytes, void* stream) {
@@ -524,4 +819,81 @@ extern "C" int idb_head_logits(const idb_head_desc* h, float* thetas, double* ro
                        (const float*)(w + p.zt), h->b, h->d, h->c, vec, lo, hi, (float)h->s, thetas);
     IDB_CHECK_LAUNCH("idb_head_logits");
     return IDB_OK;
+}
+
+extern "C" size_t idb_head_grad_workspace_bytes(int32_t b, int32_t d, int32_t c, int32_t* row_tiles, int32_t* class_blocks, int32_t* d_chunks) {
+    if (!head_dims_ok(b, d, c)) return 0;
+    const HeadGradPlan g = head_grad_plan(b, d, c);
+    if (!g.ok) return 0;
+    if (row_tiles) *row_tiles = g.row_tiles;
+    if (class_blocks) *class_blocks = g.blocks;
+    if (d_chunks) *d_chunks = g.chunks;
+    return g.total;
+}
+
+extern "C" int idb_head_loss_grad(const idb_head_desc* h, double* rows, int32_t* pred, double* mean_loss, int32_t* correct, double* grad_rows,
+                                  float* d_emb, float* d_kernel, void* ws, size_t ws_bytes, void* stream) {
+    const int rc0 = head_check("idb_head_loss_grad", h, ws, ws_bytes);
+    if (rc0 != IDB_OK) return rc0;
+    IDB_REQUIRE(rows && pred && mean_loss && correct && grad_rows && d_emb && d_kernel, "idb_head_loss_grad: null output pointer");
+    const HeadGradPlan g = head_grad_plan(h->b, h->d, h->c);
+    if (!g.ok) {
+        idb_set_error("idb_head_loss_grad: class blocks x b x d = %d x %d x %d floats of dX partials, the limit is 2^27 (512 MiB)", g.blocks,
+                      h->b, h->d);
+        return IDB_EUNSUPPORTED;
+    }
+    IDB_REQUIRE(ws_bytes >= g.total, "idb_head_loss_grad: workspace too small (idb_head_grad_workspace_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)ws;
+    const int rc = head_loss_run(h, rows, pred, mean_loss, correct, w, st);
+    if (rc != IDB_OK) return rc;
+    const HeadPlan p = head_plan(h->b, h->d, h->c);
+    const bool ada = h->kind == IDB_HEAD_ADAFACE;
+    const float* x = ada ? h->emb : (const float*)(w + p.en);
+    const float lo = ada ? (float)(-1.0 + ADA_EPS) : -1.f, hi = ada ? (float)(1.0 - ADA_EPS) : 1.f;
+    const int vec = h->d % 4 == 0 && idb_aligned16(x) && idb_aligned16(h->wn);
+    hipLaunchKernelGGL(head_grad_prep_kernel, dim3((h->b + 3) / 4), dim3(256), 0, st, h->emb, (const double*)rows, h->b, h->d,
+                       HeadMargin{h->kind, h->s, h->m, h->h}, grad_rows);
+    IDB_CHECK_LAUNCH("idb_head_loss_grad(prep)");
+    const double s_over_b = h->s / (double)h->b;
+    float* part = (float*)(w + g.part);
+    double* dot = (double*)(w + g.dot);
+#define HEAD_GRAD(DW, MULTI, GRID, PER)                                                                                                   \
+    hipLaunchKernelGGL((head_grad_kernel<DW, MULTI>), GRID, dim3(256), 0, st, x, h->wn, h->label, (const double*)rows,                      \
+                       (const double*)grad_rows, h->b, h->d, h->c, vec, lo, hi, (float)h->s, s_over_b, PER, part, dot, h->kernel, h->col_norm, \
+                       d_kernel)
+    // past one chunk of 128 columns a workgroup walks all chunks per cosine tile; dW can do so only where one row tile holds the batch
+    if (g.chunks > 1) HEAD_GRAD(false, true, dim3(g.blocks, g.row_tiles, 1), g.per);
+    else HEAD_GRAD(false, false, dim3(g.blocks, g.row_tiles, 1), g.per);
+    IDB_CHECK_LAUNCH("idb_head_loss_grad(dX)");
+    hipLaunchKernelGGL(head_grad_rows_kernel, dim3(h->b), dim3(256), 0, st, (const float*)part, (const double*)dot, h->emb,
+                       (const double*)grad_rows, g.blocks, h->b, h->d, ada ? 1 : 0, d_emb);
+    IDB_CHECK_LAUNCH("idb_head_loss_grad(rows)");
+    if (g.chunks > 1 && g.row_tiles == 1) HEAD_GRAD(true, true, dim3((h->c + HB - 1) / HB, 1, 1), 0);
+    else HEAD_GRAD(true, false, dim3((h->c + HB - 1) / HB, 1, g.chunks), 0);
+#undef HEAD_GRAD
+    IDB_CHECK_LAUNCH("idb_head_loss_grad(dW)");
+    return IDB_OK;
+}
+
+extern "C" int idb_head_sgd_step(float* kernel, const float* grad, float* momentum_buf, int32_t d, int32_t c, double lr, double momentum,
+                                 double weight_decay, double max_norm, int32_t first_step, float* wn, double* col_norm, int32_t* bad_cols,
+                                 double* total_norm, void* ws, size_t ws_bytes, void* stream) {
+    IDB_REQUIRE(head_dims_ok(1, d, c), "idb_head_sgd_step: d in 1..%d and c in 1..%d", HEAD_MAX_D, HEAD_MAX_C);
+    IDB_REQUIRE(kernel && grad && momentum_buf && wn && col_norm && bad_cols && total_norm, "idb_head_sgd_step: null pointer");
+    IDB_REQUIRE(lr >= 0.0 && lr <= 1e4 && momentum >= 0.0 && momentum < 1.0 && weight_decay >= 0.0 && weight_decay <= 1e4 && max_norm > 0.0 &&
+                    max_norm <= 1e30,
+                "idb_head_sgd_step: lr in [0, 1e4], momentum in [0, 1), weight_decay in [0, 1e4], max_norm in (0, 1e30]");
+    IDB_REQUIRE(ws && idb_aligned16(ws) && ws_bytes >= IDB_HEAD_SGD_WS_BYTES, "idb_head_sgd_step: workspace too small or unaligned (%d bytes)",
+                IDB_HEAD_SGD_WS_BYTES);
+    hipStream_t st = (hipStream_t)stream;
+    const long long n = (long long)d * c;
+    const long long want = (n + 4095) / 4096;
+    const int nparts = want < SGD_PARTS ? (int)want : SGD_PARTS;
+    hipLaunchKernelGGL(head_sqsum_kernel, dim3(nparts), dim3(256), 0, st, grad, n, (double*)ws);
+    IDB_CHECK_LAUNCH("idb_head_sgd_step(norm)");
+    hipLaunchKernelGGL(head_sgd_kernel, dim3(nparts), dim3(256), 0, st, kernel, grad, momentum_buf, n, (const double*)ws, nparts, lr, momentum,
+                       weight_decay, max_norm, first_step != 0, total_norm);
+    IDB_CHECK_LAUNCH("idb_head_sgd_step");
+    return idb_head_pack(kernel, d, c, wn, col_norm, bad_cols, stream);
 }

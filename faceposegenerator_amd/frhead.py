@@ -1,4 +1,4 @@
-"""The loss head of the reference's face-recognition training loop, forward only: the margin header (``FR_training/utils/losses.py``
+"""The loss head of the reference's face-recognition training loop, forward and backward: the margin header (``FR_training/utils/losses.py``
 ``CosFace``, ``ArcFace``, ``AdaFace``), ``CrossEntropyLoss`` and ``multi_class_acc`` (``train_FR.py:279-302``, ``:373-377``), i.e. the
 two numbers ``CallBackLogging`` prints at every step, for a checkpoint's ``<step>_backbone.pth`` / ``<step>_header.pth`` pair
 (``CallBackModelCheckpointOld``, ``utils_callbacks.py:209-239``).
@@ -20,7 +20,18 @@ non-finite column (upstream: ``0 / 0`` = NaN logits), non-finite or zero embeddi
 the call raises after it, and a NaN norm leaves AdaFace's buffers unchanged), and AdaFace on a batch of one (the unbiased
 standard deviation of one norm is NaN).
 
-Out of scope: gradients, the optimiser, ``clip_grad_norm_``, top-5 (the loop logs 0 for it), sharding C over several GPUs.
+The backward: ``header.loss_and_grad(embeddings, label)`` returns the loss and what ``accelerator.backward(loss_v)``
+(``train_FR.py:290``) leaves in ``header.kernel.grad`` and hands back through the embeddings (``idb_head_loss_grad``: the forward's
+launches, then the softmax recomputed from the saved log-sum-exp and both gradient products on the f32 MFMA; no B x C matrix, no
+floating-point atomics, bit-identical from run to run).  ``HeaderSGD`` is the loop's ``clip_grad_norm_(header.parameters(), 5)`` and
+``opt_header.step()`` (SGD, momentum 0.9, weight decay 5e-4; ``train_FR.py:203-208``, ``:293``, ``:296``) with the kernel repacked
+after every step, ``train_header_step`` the header's share of the loop body.  Off the target the derivative of
+``cos(acos(c))`` is taken as its limit 1; upstream's autograd evaluates ``sin(acos c) / sqrt(1 - c^2)`` and gives NaN at a cosine of
+exactly +-1.  A row whose target slope is not finite (an ArcFace target cosine of exactly +-1: upstream gives inf / NaN) is refused like
+the bad rows above.
+
+Out of scope: the backbone's backward (``dL/d embeddings`` is handed out, nothing here consumes it), the learning-rate schedule,
+top-5 (the loop logs 0 for it), sharding C over several GPUs.
 """
 from __future__ import annotations
 
@@ -57,6 +68,18 @@ class HeadLoss(NamedTuple):
     correct: int
     acc: float
     margin_scaler: torch.Tensor
+
+
+class HeadGrad(NamedTuple):
+    """embeddings: dL/d embeddings, fp32 [B, D]; kernel: dL/d kernel, fp32 [D, C] (the layout of kernel.grad); target_slope: float64
+    [B], dz_target / (s dcos_target) with the clamp (and AdaFace's clip) folded in: 0 where the target is clamped away."""
+    embeddings: torch.Tensor
+    kernel: torch.Tensor
+    target_slope: torch.Tensor
+
+
+_BAD_SLOPE = ("embeddings: a target cosine of exactly +-1 under ArcFace: the slope sin(acos(c) + m) / sqrt(1 - c^2) is not finite "
+              "(upstream's autograd gives inf / NaN)")
 
 
 def multi_class_acc(correct: int, batch: int) -> float:
@@ -117,7 +140,7 @@ class MarginHeader:
         norms = k.double().norm(dim=0)
         if not bool(torch.isfinite(norms).all()) or bool((norms == 0).any()):
             raise ValueError("kernel: a zero or non-finite column (upstream divides it by its norm: NaN logits)")
-        self.kernel = k
+        self._kernel_host, self._kernel_stale = k, False
         self.in_features, self.out_features = d, c
         self.s = float(s)
         self.m = float(DEFAULT_M[loss] if m is None else m)
@@ -159,6 +182,13 @@ class MarginHeader:
         per row; the direction statistics of the columns are the same)."""
         g = torch.Generator().manual_seed(seed)
         return cls(torch.randn(int(in_features), int(out_features), generator=g) * 0.01, loss, **kw)
+
+    @property
+    def kernel(self) -> torch.Tensor:
+        """The parameter, fp32 [in_features, out_features] on the host; after a HeaderSGD step it is fetched from the device."""
+        if self._kernel_stale:
+            self._kernel_host, self._kernel_stale = self._kernel_dev.cpu(), False
+        return self._kernel_host
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         sd = {"kernel": self.kernel.clone()}
@@ -272,6 +302,120 @@ class MarginHeader:
         if not math.isfinite(mean):                            # the prep launch gives a bad row a NaN target, which the mean carries
             raise ValueError(_BAD_ROWS)
         return HeadLoss(mean, rows[1], rows[0], rows[2], pred, n_ok, multi_class_acc(n_ok, d.b), rows[4])
+
+    def grad_plan(self, batch: int) -> Tuple[int, int, int]:
+        """(row tiles, class blocks, D chunks) of the backward's dX launch for a batch: idb_head_grad_workspace_bytes' geometry."""
+        rt, cb, ch = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        if _lib.load().idb_head_grad_workspace_bytes(int(batch), self.in_features, self.out_features, C.byref(rt), C.byref(cb),
+                                                     C.byref(ch)) == 0:
+            raise ValueError(f"batch {batch} x {self.in_features} x {self.out_features} classes: outside 1..{MAX_B}, or more than 2^27 "
+                             f"floats of dX partials (class blocks x batch x in_features)")
+        return rt.value, cb.value, ch.value
+
+    def loss_and_grad(self, embeddings, label, norms=None) -> Tuple[HeadLoss, "HeadGrad"]:
+        """header.loss(...) and the gradients of its mean loss w.r.t. the embeddings and the kernel, in one call (AdaFace's buffers
+        advance once, `norms` is detached as upstream).  Neither the probabilities nor their gradient are ever written."""
+        lib, d, keep, _ = self._desc(embeddings, label, norms)
+        dev = self.device
+        need = lib.idb_head_grad_workspace_bytes(d.b, d.d, d.c, None, None, None)
+        if need == 0:
+            raise ValueError(f"loss_and_grad: batch {d.b} x {d.d} x {d.c} classes needs more than 2^27 floats of dX partials (class "
+                             f"blocks x batch x in_features): split the batch")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        rows = torch.empty((5, d.b), dtype=torch.float64, device=dev)
+        grad_rows = torch.empty((3, d.b), dtype=torch.float64, device=dev)
+        pred = torch.empty(d.b, dtype=torch.int32, device=dev)
+        d_emb = torch.empty((d.b, d.d), dtype=torch.float32, device=dev)
+        d_kernel = torch.empty((d.d, d.c), dtype=torch.float32, device=dev)
+        both = torch.zeros(16, dtype=torch.uint8, device=dev)
+        _lib.check(lib.idb_head_loss_grad(C.byref(d), rows.data_ptr(), pred.data_ptr(), both.data_ptr(), both.data_ptr() + 8,
+                                          grad_rows.data_ptr(), d_emb.data_ptr(), d_kernel.data_ptr(), ws.data_ptr(), need,
+                                          torch.cuda.current_stream(dev).cuda_stream), "idb_head_loss_grad")
+        host = both.cpu()
+        mean, n_ok = float(host[:8].view(torch.float64)[0]), int(host[8:12].view(torch.int32)[0])
+        if not math.isfinite(mean):
+            raise ValueError(_BAD_ROWS)
+        if not bool(torch.isfinite(grad_rows[0]).all()):
+            raise ValueError(_BAD_SLOPE)
+        out = HeadLoss(mean, rows[1], rows[0], rows[2], pred, n_ok, multi_class_acc(n_ok, d.b), rows[4])
+        return out, HeadGrad(d_emb, d_kernel, grad_rows[0])
+
+
+class HeaderSGD:
+    """The header's optimiser of train_FR.py: clip_grad_norm_(header.parameters(), max_norm) (:293), then torch.optim.SGD(lr, momentum,
+    weight_decay).step() (:203-208, :296) on header.kernel, fp32 state as torch, one call (idb_head_sgd_step); the header is repacked
+    inside it, so the next forward sees the stepped kernel.  `lr` may be reassigned between steps (the loop's scheduler)."""
+
+    def __init__(self, header: MarginHeader, lr: float, momentum: float = 0.9, weight_decay: float = 5e-4, max_norm: float = 5.0):
+        if not isinstance(header, MarginHeader):
+            raise TypeError("HeaderSGD: header must be a MarginHeader")
+        self.lr, self.momentum, self.weight_decay, self.max_norm = float(lr), float(momentum), float(weight_decay), float(max_norm)
+        if not (0.0 <= self.lr <= 1e4 and 0.0 <= self.momentum < 1.0 and 0.0 <= self.weight_decay <= 1e4 and 0.0 < self.max_norm <= 1e30):
+            raise ValueError("HeaderSGD: lr in [0, 1e4], momentum in [0, 1), weight_decay in [0, 1e4], max_norm in (0, 1e30]")
+        self.header = header
+        self.steps = 0
+        self._buf: Optional[torch.Tensor] = None
+
+    def state_dict(self) -> Dict[str, object]:
+        """{"lr", "momentum", "weight_decay", "max_norm", "steps", "momentum_buffer" (fp32 [D, C] on the host, None before a step)}."""
+        return {"lr": self.lr, "momentum": self.momentum, "weight_decay": self.weight_decay, "max_norm": self.max_norm,
+                "steps": self.steps, "momentum_buffer": None if self._buf is None else self._buf.detach().cpu().clone()}
+
+    def load_state_dict(self, sd) -> None:
+        missing = [k for k in ("lr", "momentum", "weight_decay", "max_norm", "steps", "momentum_buffer") if k not in sd]
+        if missing:
+            raise ValueError(f"HeaderSGD state dict without {missing}")
+        buf, steps = sd["momentum_buffer"], int(sd["steps"])
+        shape = (self.header.in_features, self.header.out_features)
+        if (buf is None) != (steps == 0):
+            raise ValueError("HeaderSGD state dict: a momentum buffer exists exactly after the first step")
+        if buf is not None and (not torch.is_tensor(buf) or tuple(buf.shape) != shape):
+            raise ValueError(f"HeaderSGD state dict: momentum_buffer expected {shape}")
+        self.lr, self.momentum, self.weight_decay, self.max_norm = (float(sd[k]) for k in ("lr", "momentum", "weight_decay", "max_norm"))
+        self.steps = steps
+        self._buf = None if buf is None else buf.detach().to(torch.float32).contiguous().clone()
+
+    def step(self, grad_kernel: torch.Tensor) -> float:
+        """One clipped SGD step on header.kernel with `grad_kernel` (fp32 [D, C], HeadGrad.kernel).  Returns the gradient's L2 norm
+        before clipping, as clip_grad_norm_ does."""
+        hd = self.header
+        if hd.device is None:
+            raise _lib.IdbError("HeaderSGD.step: the header is not on a device: call .to('cuda:0') first (there is no CPU fallback)")
+        shape = (hd.in_features, hd.out_features)
+        if not torch.is_tensor(grad_kernel) or tuple(grad_kernel.shape) != shape or grad_kernel.dtype != torch.float32:
+            raise ValueError(f"HeaderSGD.step: grad_kernel expected fp32 {shape}")
+        dev = hd.device
+        g = grad_kernel.to(dev).contiguous()
+        first = self._buf is None
+        if first:
+            self._buf = torch.empty(shape, dtype=torch.float32, device=dev)
+        elif self._buf.device != dev:
+            self._buf = self._buf.to(dev)
+        ws = torch.empty(_lib.IDB_HEAD_SGD_WS_BYTES, dtype=torch.uint8, device=dev)
+        both = torch.zeros(16, dtype=torch.uint8, device=dev)      # bytes 0-7 the norm (double), 8-11 the bad columns (int32): one read
+        lib = _lib.load()
+        _lib.check(lib.idb_head_sgd_step(hd._kernel_dev.data_ptr(), g.data_ptr(), self._buf.data_ptr(), shape[0], shape[1], self.lr,
+                                         self.momentum, self.weight_decay, self.max_norm, 1 if first else 0, hd._wn.data_ptr(),
+                                         hd._col_norm.data_ptr(), both.data_ptr() + 8, both.data_ptr(), ws.data_ptr(),
+                                         _lib.IDB_HEAD_SGD_WS_BYTES, torch.cuda.current_stream(dev).cuda_stream), "idb_head_sgd_step")
+        hd._kernel_stale = True
+        self.steps += 1
+        host = both.cpu()
+        norm, bad = float(host[:8].view(torch.float64)[0]), int(host[8:12].view(torch.int32)[0])
+        if bad != 0 or not math.isfinite(norm):
+            raise ValueError(f"HeaderSGD.step: the step left {bad} zero or non-finite kernel column(s) (gradient norm {norm})")
+        return norm
+
+
+def train_header_step(header: MarginHeader, opt: HeaderSGD, embeddings, labels, norms=None) -> Dict[str, object]:
+    """The header's share of the loop body (train_FR.py:286-298): forward, loss, backward, clip_grad_norm_, opt_header.step().  Returns
+    {"loss", "acc", "correct", "grad_embeddings" (fp32 [B, D], for whatever trains the backbone), "grad_norm" (before clipping)}; the
+    loss and accuracy are those of the kernel BEFORE the step, as the loop logs them."""
+    if not isinstance(header, MarginHeader) or not isinstance(opt, HeaderSGD) or opt.header is not header:
+        raise TypeError("train_header_step: expected a MarginHeader and the HeaderSGD built on it")
+    out, grad = header.loss_and_grad(embeddings, labels, norms=norms)
+    norm = opt.step(grad.kernel)
+    return {"loss": out.loss, "acc": out.acc, "correct": out.correct, "grad_embeddings": grad.embeddings, "grad_norm": norm}
 
 
 def step_metrics(backbone, header: MarginHeader, images, labels, training: bool = False) -> Dict[str, float]:

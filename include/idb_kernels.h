@@ -745,6 +745,41 @@ int idb_head_loss(const idb_head_desc* h, double* rows, int32_t* pred, double* m
                   void* stream);
 int idb_head_logits(const idb_head_desc* h, float* thetas, double* rows, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The loss head's backward and the header's optimiser step: what `accelerator.backward(loss_v)` (train_FR.py:290) leaves in
+ * `header.kernel.grad` and hands back through the embeddings, then `clip_grad_norm_(header.parameters(), 5)` and `opt_header.step()`
+ * (train_FR.py:293, :296; SGD with momentum 0.9 and weight decay 5e-4, :203-208).  The b x c matrix is never written, neither the
+ * probabilities nor their gradient; no floating-point atomics, every sum in an order the shapes alone decide.
+ *   With r_ij the raw cosine, (lo, hi) the forward's clamp, p_ij = exp(z_ij - lse_i) from the forward's log-sum-exp and
+ *   G_ij = (p_ij - [j == label_i]) / b * s * d_ij * [lo <= r_ij <= hi] (inclusive, as torch's clamp backward), where d_ij = 1 off the
+ *   target (the limit of sin(acos c) / sqrt(1 - c^2), which upstream evaluates to NaN at c = +-1 exactly) and the target's slope is
+ *     CosFace 1      ArcFace sin(acos(c) + m) / sqrt(1 - c^2)
+ *     AdaFace sin(t) / sqrt(1 - c^2) with t = acos(c) - m scaler if e <= t <= pi - e, else 0 (c after the clamp),
+ *   d_emb_i = (dX_i - x_i <x_i, dX_i>) / |e_i| with dX = G Wn (AdaFace: dX_i, its rows are taken as they are and `norms` is detached),
+ *   d_kernel[:, j] = (dW_j - w_j <w_j, dW_j>) / col_norm[j] with dW = G^T X; both projections and divisions in double, one rounding.
+ *   idb_head_grad_workspace_bytes(b, d, c, row_tiles, class_blocks, d_chunks): the workspace of idb_head_loss_grad (the forward's
+ *       included), 0 for shapes it refuses: those of idb_head_workspace_bytes, and class_blocks * b * d > 2^27 floats (512 MiB) of dX
+ *       partials.  The three outputs (any may be NULL) receive the dX launch's grid: tiles of 128 rows, blocks of classes whose
+ *       partial dX rows are merged in ascending order, and chunks of 128 columns of d (walked inside a
+ *       workgroup after each cosine tile; with several row tiles the dW launch gives every chunk its own workgroups).
+ *   idb_head_loss_grad: idb_head_loss (same launches, same values, AdaFace's buffers updated ONCE), then: per-row slopes, dX tiles,
+ *       dX merge + projection, dW tiles + projection.  grad_rows: double [3][b]: the target's slope d_i with its clamp / clip mask
+ *       folded in (not finite for an ArcFace target cosine of +-1 exactly: callers refuse), that mask, |e_i|.  d_emb: fp32 [b][d].
+ *       d_kernel: fp32 [d][c], as torch stores kernel.grad.  Arguments as idb_head_loss; IDB_EUNSUPPORTED past the partials' limit.
+ *   idb_head_sgd_step: total_norm = |grad|_2 (double, fixed order; written to total_norm [1] on the device),
+ *       coef = min(1, max_norm / (total_norm + 1e-6)), g = coef grad + weight_decay kernel, momentum_buf = g on the first step, else
+ *       momentum momentum_buf + g, kernel -= lr momentum_buf (each element in double, each fp32 state rounded once), then
+ *       idb_head_pack(kernel, ...) so that wn / col_norm / bad_cols follow the kernel.  kernel, grad, momentum_buf: fp32 [d][c].
+ *       ws: IDB_HEAD_SGD_WS_BYTES, 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+#define IDB_HEAD_SGD_WS_BYTES 8192
+size_t idb_head_grad_workspace_bytes(int32_t b, int32_t d, int32_t c, int32_t* row_tiles, int32_t* class_blocks, int32_t* d_chunks);
+int idb_head_loss_grad(const idb_head_desc* h, double* rows, int32_t* pred, double* mean_loss, int32_t* correct, double* grad_rows,
+                       float* d_emb, float* d_kernel, void* ws, size_t ws_bytes, void* stream);
+int idb_head_sgd_step(float* kernel, const float* grad, float* momentum_buf, int32_t d, int32_t c, double lr, double momentum,
+                      double weight_decay, double max_norm, int32_t first_step, float* wn, double* col_norm, int32_t* bad_cols,
+                      double* total_norm, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
