@@ -19,6 +19,8 @@ IDB_PLMS_SLOTS = 4
 IDB_PLMS_KEEP, IDB_PLMS_SAVE, IDB_PLMS_RESTORE = 0, 1, 2
 IDB_HEAD_COSFACE, IDB_HEAD_ARCFACE, IDB_HEAD_ADAFACE = 0, 1, 2
 IDB_HEAD_SGD_WS_BYTES = 8192
+IDB_SGD_CLIP_WS_BYTES = 65536
+IDB_SGD_CLIP_MAX_TENSORS = 8
 IDB_PAIR_DIST2, IDB_PAIR_KNN, IDB_PAIR_PRDC, IDB_PAIR_NEAREST, IDB_PAIR_POLY = 0, 1, 2, 3, 4
 # the selected points of idb_verif_roc, in the order of its points / ints outputs
 IDB_VERIF_POINTS = ("eer_t2", "eer_t1", "fmr0", "fmr1000", "fmr100", "fmr20", "fmr10", "fnmr0", "fnmr100", "fnmr1000", "youden", "mcc", "first")
@@ -47,6 +49,7 @@ EXPORTS = [
     "idb_randaug",
     "idb_head_pack", "idb_head_workspace_bytes", "idb_head_loss", "idb_head_logits",
     "idb_head_grad_workspace_bytes", "idb_head_loss_grad", "idb_head_sgd_step",
+    "idb_tail_workspace_bytes", "idb_tail_forward", "idb_tail_backward", "idb_sgd_clip_step",
 ]
 
 
@@ -85,6 +88,14 @@ class HeadDesc(C.Structure):
                 ("s", C.c_double), ("m", C.c_double), ("h", C.c_double), ("t_alpha", C.c_double),
                 ("emb", C.c_void_p), ("norms", C.c_void_p), ("label", C.c_void_p), ("kernel", C.c_void_p),
                 ("wn", C.c_void_p), ("col_norm", C.c_void_p), ("ada_state", C.c_void_p)]
+
+
+class TailDesc(C.Structure):
+    _fields_ = [("b", C.c_int32), ("ch", C.c_int32), ("hw", C.c_int32), ("n", C.c_int32), ("x_dtype", C.c_int32), ("training", C.c_int32),
+                ("p", C.c_double), ("eps2", C.c_double), ("eps1", C.c_double), ("momentum", C.c_double),
+                ("x", C.c_void_p), ("keep", C.c_void_p), ("bn2_weight", C.c_void_p), ("bn2_bias", C.c_void_p), ("bn2_mean", C.c_void_p),
+                ("bn2_var", C.c_void_p), ("fc_weight", C.c_void_p), ("fc_bias", C.c_void_p), ("feat_weight", C.c_void_p),
+                ("feat_bias", C.c_void_p), ("feat_mean", C.c_void_p), ("feat_var", C.c_void_p)]
 
 
 class IdbError(RuntimeError):
@@ -194,6 +205,11 @@ def load() -> C.CDLL:
         "idb_head_grad_workspace_bytes": (sz, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "idb_head_loss_grad": (C.c_int, [C.POINTER(HeadDesc), vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "idb_head_sgd_step": (C.c_int, [vp, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, i32, vp, vp, vp, vp, vp, sz,
+                                        vp]),
+        "idb_tail_workspace_bytes": (sz, [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
+        "idb_tail_forward": (C.c_int, [C.POINTER(TailDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "idb_tail_backward": (C.c_int, [C.POINTER(TailDesc)] + [vp] * 8 + [i32] + [vp] * 7 + [sz, vp]),
+        "idb_sgd_clip_step": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)] + [C.c_double] * 4 + [i32, vp, vp, sz,
                                         vp]),
     }
     for name, (res, args) in sig.items():

@@ -274,6 +274,28 @@ class ArcFace(N.HipNet):
         self._need_device()
         return self._run(t.to(self.device).contiguous(), True)
 
+    def _features(self, x: torch.Tensor, u8: bool) -> torch.Tensor:
+        x, xb = self.stem(x, u8)
+        for i in range(4):
+            x, xb = self.stage(i, x, xb)
+        return x
+
+    def features_map(self, x: torch.Tensor) -> torch.Tensor:
+        """float [B,3,112,112] as __call__ takes it -> layer4's output, NHWC [B,7,7,512] in the operand dtype: what the embedding
+        stage (frtail.EmbeddingStage) starts from.  The trunk is the folded eval network."""
+        if not torch.is_tensor(x) or x.ndim != 4 or tuple(x.shape[1:]) != (3, SIZE, SIZE) or x.shape[0] < 1:
+            raise ValueError(f"ArcFace expects [B,3,{SIZE},{SIZE}] input (the fc fixes 7x7), got {tuple(getattr(x, 'shape', ()))}")
+        self._need_device()
+        return self._chunked(x.to(self.device, dtype=torch.float32).contiguous(), lambda xc: (self._features(xc, False),))[0]
+
+    def features_map_u8(self, crops) -> torch.Tensor:
+        """uint8 NHWC [B,112,112,3] aligned crops -> NHWC [B,7,7,512], the preprocessing on the GPU."""
+        t = torch.as_tensor(np.asarray(crops)) if not torch.is_tensor(crops) else crops
+        if t.dtype != torch.uint8 or t.ndim != 4 or tuple(t.shape[1:]) != (SIZE, SIZE, 3) or t.shape[0] < 1:
+            raise ValueError(f"features_map_u8 expects uint8 [B,{SIZE},{SIZE},3] crops, got {t.dtype} {tuple(t.shape)}")
+        self._need_device()
+        return self._chunked(t.to(self.device).contiguous(), lambda xc: (self._features(xc, True),))[0]
+
 
 def embed_faces(images_u8, mtcnn, arcface: ArcFace):
     """detect(..., landmarks=True) -> norm_crop of the first (largest) face -> embed_u8, for a uint8 NHWC image batch.

@@ -30,7 +30,7 @@ after every step, ``train_header_step`` the header's share of the loop body.  Of
 exactly +-1.  A row whose target slope is not finite (an ArcFace target cosine of exactly +-1: upstream gives inf / NaN) is refused like
 the bad rows above.
 
-Out of scope: the backbone's backward (``dL/d embeddings`` is handed out, nothing here consumes it), the learning-rate schedule,
+Out of scope: the convolutional trunk's backward (``dL/d embeddings`` is consumed by ``frtail.EmbeddingStage.backward``),
 top-5 (the loop logs 0 for it), sharding C over several GPUs.
 """
 from __future__ import annotations

@@ -780,6 +780,73 @@ int idb_head_sgd_step(float* kernel, const float* grad, float* momentum_buf, int
                       double weight_decay, double max_norm, int32_t first_step, float* wn, double* col_norm, int32_t* bad_cols,
                       double* total_norm, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The backbone's embedding stage in training (ID-Booth's FR_training/backbones/iresnet.py: bn2 -> flatten -> dropout -> fc ->
+ * features, then train_FR.py's F.normalize), forward and backward, and the loop's joint clip_grad_norm_ + SGD step over a list of
+ * tensors.  fp32 state and operands on the exact f32-input MFMA; every statistic and reduction in double in an order the shapes
+ * alone decide; no floating-point atomics (bit-identical from run to run); no synchronisation; every argument is validated before
+ * any HIP call.
+ *   Layout: x is NHWC [b][hw][ch] in x_dtype; with K = hw ch and k = p ch + c, sample i's flattened row is x[i K + k].  fc_weight is
+ *   fp32 [n][K] with that column order (upstream's is c hw + p), as are its gradient, the uint8 keep-mask [b][K] and d_x.
+ *   2 <= b <= 1024 in training (1 <= b in eval), ch % 64 == 0 <= 2048, 1 <= hw <= 64, n % 64 == 0 <= 1024, 0 <= p < 1.
+ *   idb_tail_workspace_bytes(b, ch, hw, n, k_slices, row_tiles): the workspace of forward and backward, 0 for refused shapes; the
+ *       outputs (either may be NULL) receive the fc forward's split over K and the tiles of 128 rows.
+ *   idb_tail_forward.  Training: per channel over the b hw rows mean and biased variance (shifted sums in double; the slices in
+ *       ascending order), invstd = 1 / sqrt(var + eps2), running_mean / running_var <- (1 - momentum) old + momentum new (the unbiased
+ *       variance, in double, rounded once); the fp32 affine sc = gamma invstd, sh = beta - mean sc (each rounded once);
+ *       d = fma(x, sc, sh) * (keep ? 1 / (1 - p) : 0) formed in the product's load path and never written (keep == NULL: all kept);
+ *       z = d W^T over K slices merged in ascending order in double, plus fc_bias, rounded once; features: the same statistics over
+ *       the batch per feature with eps1; f = (z - mean) invstd feat_weight + feat_bias in double, rounded once;
+ *       norm = |f| (double, of the rounded row); emb = f / max(norm, 1e-12).  Eval: both BatchNorms use their running statistics,
+ *       which stay unchanged; keep must be NULL.
+ *       Outputs: emb fp32 [b][n], norms double [b], bn2_stat double [2][ch] (mean, invstd), affine fp32 [2][ch] (sc, sh; 16-byte
+ *       aligned), z fp32 [b][n], feat_stat double [2][n], f fp32 [b][n], flags int32 [4] (device): [0] a statistic or, in either mode, a row's norm is not finite
+ *       (a NaN or infinity in x), [1] / [2] a bn2 / features variance of exactly 0 with eps = 0.  Callers refuse on any flag.
+ *   idb_tail_backward (training descriptors only), given g_emb fp32 [b][n] and the forward's outputs:
+ *       renormalised: g <- (g - y <y, g>) / |emb| with y = emb / |emb| (the loop's AdaFace branch); g_f = (g - u <u, g>) / norm with
+ *       u = f / norm; S1 = sum_b g_f, S2 = sum_b g_f zhat; g_z = feat_weight invstd (g_f - S1 / b - zhat S2 / b), fp32;
+ *       d_feat_bias = S1, d_fc_bias = sum_b g_z; g_y = (g_z W) (keep ? 1 / (1 - p) : 0), fp32 [b][K] in the workspace, with per
+ *       (row tile, k) partial sums of g_y and g_y xhat merged over tiles then positions in ascending order: d_bn2_bias, d_bn2_weight;
+ *       d_x = gamma invstd (g_y - mean(g_y) - xhat mean(g_y xhat)), fp32 [b][K] (NULL: that launch is skipped);
+ *       d_fc_weight[j][k] = sum_b g_z[b][j] d[b][k] with d recomputed as in the forward, the batch ascending inside one workgroup.
+ *   idb_sgd_clip_step: clip_grad_norm_(params, max_norm) and torch.optim.SGD(momentum, weight_decay).step() over 1..8 fp32
+ *       tensors given as host arrays of device pointers: total_norm = the L2 norm over all gradients (double partials per tensor,
+ *       tensor after tensor; written to total_norm [1] on the device), then idb_head_sgd_step's arithmetic per element without the
+ *       repack.  ws: IDB_SGD_CLIP_WS_BYTES, 16-byte aligned; total_norm 8-byte aligned; no weight or momentum buffer may appear
+ *       twice in the lists (IDB_EINVAL).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct idb_tail_desc {
+    int32_t b, ch, hw, n;
+    int32_t x_dtype;          /* IDB_F16, IDB_BF16 or IDB_F32 */
+    int32_t training;         /* 1: batch statistics, dropout, running statistics updated; 0: running statistics */
+    double p;                 /* dropout probability */
+    double eps2, eps1;        /* bn2's and features' eps */
+    double momentum;          /* of both BatchNorms */
+    const void* x;            /* [b][hw][ch] */
+    const uint8_t* keep;      /* [b][hw ch], training only; NULL: nothing dropped */
+    const float* bn2_weight;  /* [ch] */
+    const float* bn2_bias;
+    float* bn2_mean;          /* running statistics [ch]: read, and updated in training */
+    float* bn2_var;
+    const float* fc_weight;   /* [n][hw ch], column p ch + c */
+    const float* fc_bias;     /* [n] */
+    const float* feat_weight; /* [n], frozen upstream */
+    const float* feat_bias;
+    float* feat_mean;         /* running statistics [n] */
+    float* feat_var;
+} idb_tail_desc;
+#define IDB_SGD_CLIP_WS_BYTES 65536
+size_t idb_tail_workspace_bytes(int32_t b, int32_t ch, int32_t hw, int32_t n, int32_t* k_slices, int32_t* row_tiles);
+int idb_tail_forward(const idb_tail_desc* d, float* emb, double* norms, double* bn2_stat, float* affine, float* z, double* feat_stat, float* f,
+                     int32_t* flags, void* ws, size_t ws_bytes, void* stream);
+int idb_tail_backward(const idb_tail_desc* d, const float* g_emb, const float* emb, const double* norms, const double* bn2_stat,
+                      const float* affine, const float* z, const double* feat_stat, const float* f, int32_t renormalised, float* d_bn2_weight,
+                      float* d_bn2_bias, float* d_fc_weight, float* d_fc_bias, float* d_feat_bias, float* d_x, void* ws, size_t ws_bytes,
+                      void* stream);
+int idb_sgd_clip_step(int32_t count, float* const* weights, const float* const* grads, float* const* momentum_bufs, const int64_t* numel,
+                      double lr, double momentum, double weight_decay, double max_norm, int32_t first_step, double* total_norm, void* ws,
+                      size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
