@@ -27,6 +27,10 @@
 //     K range of a split, K seek and row decode are multiply-highs by exact reciprocals or shifts, the patch conv's H / nimg / RI
 //     and the GroupNorm's group width arrive as values (a batch-1 launch is ~14 us, and 7-12 division expansions stood on every
 //     loader wave's path to its first LDS-DMA).  Quotients, and with them every address and K range, are what they were.
+//   * kernel arguments are laid out by when they are needed (idb_gemm_epi.h: GemmTile, GemmHead): the launch scalars of the tile index,
+//     the K range and the K seek's source are leading plain parameters, preloaded into SGPRs at wave launch (Makefile: KERNARG_PRELOAD);
+//     the loader waves and the ring kernel fetch the head and the source record of their first K-step as three 16-dword scalar loads
+//     behind ONE wait (a lone workgroup per CU stood through 6-7 dependent kernel-argument round trips before its first LDS-DMA).
 #include "idb_common.h"
 #include <stdlib.h>
 
@@ -37,14 +41,16 @@
 // idb_gemm_kernel and its ReLU twin (idb_gemm_desc.act = 3) share one body (idb_gemm_ring_body.inc); the epilogue activation is a
 // compile-time parameter, so the kernels without it keep their code and register budgets.
 template <typename T, int MF, int NF, int NS, int WM = 2>   // WM wave rows x 2 wave columns; tile = (16*MF*WM) x (32*NF)
-__global__ __launch_bounds__(128 * WM, 2) void idb_gemm_kernel(const GemmParams p) {
+__global__ __launch_bounds__(128 * WM, 2) void idb_gemm_kernel(IDB_TILE_PARAMS, const GemmParams p) {
     [[maybe_unused]] constexpr bool RELU = false;
+    [[maybe_unused]] const GemmTile h = IDB_TILE_PACK;
 #include "idb_gemm_ring_body.inc"
 }
 
 template <typename T, int MF, int NF, int NS, int WM = 2>
-__global__ __launch_bounds__(128 * WM, 2) void idb_gemm_kernel_relu(const GemmParams p) {
+__global__ __launch_bounds__(128 * WM, 2) void idb_gemm_kernel_relu(IDB_TILE_PARAMS, const GemmParams p) {
     [[maybe_unused]] constexpr bool RELU = true;
+    [[maybe_unused]] const GemmTile h = IDB_TILE_PACK;
 #include "idb_gemm_ring_body.inc"
 }
 
@@ -65,7 +71,7 @@ __global__ __launch_bounds__(128 * WM, 2) void idb_gemm_kernel_relu(const GemmPa
 //   it+NS-2 stay in flight), the barrier publishes it and proves stage it-1 is read, then they issue stage it+NS-1 into that buffer.
 // ------------------------------------------------------------------------------------------------------------
 template <typename T, int MF, int NF, int NS, int WM, int LW, bool RELU>
-__device__ __forceinline__ void idb_gemm_kernel_lw_body(const GemmParams& p) {
+__device__ __forceinline__ void idb_gemm_kernel_lw_body(const GemmTile& h, const GemmParams& p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using V8 = typename Op<T>::v8;
     constexpr int BM = 16 * MF * WM, BN = 32 * NF;
@@ -82,11 +88,11 @@ __device__ __forceinline__ void idb_gemm_kernel_lw_body(const GemmParams& p) {
     const bool loader = wave >= 2 * WM;                        // wave-uniform (readfirstlane): a scalar branch, not an EXEC mask
 
     int wg, kz, tm, tn;
-    idb_wg_tile(p, wg, kz);
-    idb_tile_mn(p, wg, tm, tn);
+    idb_wg_tile(h, wg, kz);
+    idb_tile_mn(h, wg, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     int kt0, kt1;
-    idb_k_range(p, kz, kt0, kt1);
+    idb_k_range(h, kz, kt0, kt1);
     const int nk = kt1 - kt0;
 
     if (loader) {
@@ -97,33 +103,38 @@ __device__ __forceinline__ void idb_gemm_kernel_lw_body(const GemmParams& p) {
         const unsigned cg16 = ((lt & 7) ^ (lrow & 7)) * 16;    // swizzle on the source side (LR is a multiple of 8)
         // First DMA first: the A half of stage 0 is requested as soon as the K seek and the row decode allow; the weight offsets, the
         // weight descriptor and the grouped-weight arithmetic — which only the W half needs — come behind it.
-        int s, tap, c0, cur_c = 64, tap_end = 9;
-        idb_k_seek(p, kt0, s, tap, c0);
+        // The source of the first K-step comes out of GemmTile alone, so the head and that source's record are requested together and
+        // waited for once (idb_loader_head); from here to the first DMA the loaders read `q` and `S`, not the kernel-argument segment.
+        int s, rem, tap, c0, cur_c = 64, tap_end = 9;
+        idb_k_seek_src(h, kt0, s, rem);
+        GemmHead q;
+        GemmSrcK S;
+        idb_loader_head(p, s, q, S);
+        idb_k_seek_tap(S, rem, tap, c0);
         int a_b[NA], a_oy[NA], a_ox[NA];
         bool a_ok[NA];
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int m = m0 + i * LR + lrow;
-            a_ok[i] = m < p.M;
-            idb_row_decode(p, a_ok[i] ? m : 0, a_b[i], a_oy[i], a_ox[i]);
+            a_ok[i] = m < q.M;
+            idb_row_decode(q, a_ok[i] ? m : 0, a_b[i], a_oy[i], a_ox[i]);
         }
         __amdgpu_buffer_rsrc_t rs_a, rs_w;
         unsigned a_voff[NA], w_voff[NJ];
-        unsigned w_soff = (unsigned)kt0 * p.w_kstep;
+        unsigned w_soff = (unsigned)kt0 * q.w_kstep;
         bool need_retap = true;
         auto stage_a = [&](int buf) {
             char* sA = smem + buf * STAGE;
             if (need_retap) {
-                const GemmSrcK S = p.src[s];
                 rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)S.ptr, 0, S.bytes, IDB_RSRC_FLAGS);
                 cur_c = S.C;
                 tap_end = S.taps == 9 ? 9 : 5;
                 const int t3 = tap / 3;
-                const int dy = t3 - p.pad, dx = tap - t3 * 3 - p.pad;
+                const int dy = t3 - q.pad, dx = tap - t3 * 3 - q.pad;
                 const int LH = S.H << S.up, LWd = S.W << S.up;
 #pragma unroll
                 for (int i = 0; i < NA; ++i) {
-                    const int iy = a_oy[i] * p.stride + dy, ix = a_ox[i] * p.stride + dx;
+                    const int iy = a_oy[i] * q.stride + dy, ix = a_ox[i] * q.stride + dx;
                     const bool ok = a_ok[i] && (unsigned)iy < (unsigned)LH && (unsigned)ix < (unsigned)LWd;
                     const int pix = (a_b[i] * S.H + (iy >> S.up)) * S.W + (ix >> S.up);
                     a_voff[i] = ok ? (unsigned)pix * (unsigned)(S.C * 2) + cg16 : IDB_OOB;
@@ -140,23 +151,23 @@ __device__ __forceinline__ void idb_gemm_kernel_lw_body(const GemmParams& p) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, LDS_PTR(sB + (j * 64 * LW + lw * 64) * 16), 16, w_voff[j], w_soff, 0, 0);
-            w_soff += p.w_kstep;
+            w_soff += q.w_kstep;
             c0 += 64;
             if (c0 == cur_c) {
                 c0 = 0;
                 need_retap = true;
                 if (++tap == tap_end) {
-                    if (s < IDB_MAX_SRC - 1) ++s;
-                    tap = p.src[s].taps == 9 ? 0 : 4;
+                    if (s < IDB_MAX_SRC - 1) S = p.src[++s];
+                    tap = S.taps == 9 ? 0 : 4;
                 }
             }
         };
         if (nk > 0) stage_a(0);
-        rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w + idb_weight_group(p, m0) * p.w_group_stride), 0, p.w_bytes, IDB_RSRC_FLAGS);
+        rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)(q.w + idb_weight_group(q, m0) * q.w_group_stride), 0, q.w_bytes, IDB_RSRC_FLAGS);
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int n = n0 + j * LR + lrow;
-            w_voff[j] = (n < p.N && j * LR + lrow < BN) ? (unsigned)(n >> 4) * p.w_blk_bytes + (unsigned)(n & 15) * p.w_row_bytes + cg16 : IDB_OOB;
+            w_voff[j] = (n < q.N && j * LR + lrow < BN) ? (unsigned)(n >> 4) * q.w_blk_bytes + (unsigned)(n & 15) * q.w_row_bytes + cg16 : IDB_OOB;
         }
         if (nk > 0) stage_w(0);
         auto stage = [&](int buf) {
@@ -279,13 +290,13 @@ __device__ __forceinline__ void idb_gemm_kernel_lw_body(const GemmParams& p) {
 }
 
 template <typename T, int MF, int NF, int NS, int WM, int LW>
-__global__ __launch_bounds__(128 * WM + 64 * LW) void idb_gemm_kernel_lw(const GemmParams p) {
-    idb_gemm_kernel_lw_body<T, MF, NF, NS, WM, LW, false>(p);
+__global__ __launch_bounds__(128 * WM + 64 * LW) void idb_gemm_kernel_lw(IDB_TILE_PARAMS, const GemmParams p) {
+    idb_gemm_kernel_lw_body<T, MF, NF, NS, WM, LW, false>(IDB_TILE_PACK, p);
 }
 
 template <typename T, int MF, int NF, int NS, int WM, int LW>
-__global__ __launch_bounds__(128 * WM + 64 * LW) void idb_gemm_kernel_lw_relu(const GemmParams p) {
-    idb_gemm_kernel_lw_body<T, MF, NF, NS, WM, LW, true>(p);
+__global__ __launch_bounds__(128 * WM + 64 * LW) void idb_gemm_kernel_lw_relu(IDB_TILE_PARAMS, const GemmParams p) {
+    idb_gemm_kernel_lw_body<T, MF, NF, NS, WM, LW, true>(IDB_TILE_PACK, p);
 }
 
 
@@ -305,14 +316,17 @@ __global__ __launch_bounds__(128 * WM + 64 * LW) void idb_gemm_kernel_lw_relu(co
 // The accumulation order over K differs from the tap-major kernels, so results are equal to rounding, not bit-identical.
 // ------------------------------------------------------------------------------------------------------------
 // K-step g of the chunk-major K walk ([segment][chunk][tap]) -> segment s, chunk c, tap t, K-step base of that segment's weights
-__device__ __forceinline__ void idb_patch_seek(const GemmParams& p, int g, int& s, int& c, int& t, int& base) {
+__device__ __forceinline__ void idb_patch_seek(const GemmTile& h, const GemmParams& p, int g, int& s, int& c, int& t, int& base) {
+    const int st[IDB_MAX_SRC - 1] = {h.st01 & 0xffff, (int)((unsigned)h.st01 >> 16), h.mode_st2 & 0xffff};   // no load in front of s
     s = 0;
     base = 0;
-    while (s < IDB_MAX_SRC - 1 && g >= p.src[s].steps) {
-        const int steps = p.src[s].steps;
-        g -= steps;
-        base += steps;
-        ++s;
+#pragma unroll
+    for (int q = 0; q < IDB_MAX_SRC - 1; ++q) {
+        if (s == q && g >= st[q]) {
+            g -= st[q];
+            base += st[q];
+            ++s;
+        }
     }
     const int taps = p.src[s].taps;                            // 9 or 1: a division by a literal is a multiply-high
     c = taps == 9 ? g / 9 : g;
@@ -395,7 +409,7 @@ __device__ __forceinline__ typename Op<T>::v8 idb_gn_norm8(typename Op<T>::v8 r,
 // tap-major idb_gemm_kernel_gn re-normalises every pixel for each of its nine taps and lost on every 3x3 conv); padding pixels stay zero.
 // Every K segment is a normalised 3x3 source and a tile lies inside one sample (host: gemm_fuses_gn).
 template <typename T, int MF, int NF, int NS, bool GN = false>
-__global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const GemmParams p) {
+__global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(IDB_TILE_PARAMS, const GemmParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using V8 = typename Op<T>::v8;
     constexpr int WM = 4;
@@ -413,16 +427,17 @@ __global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const Ge
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const GemmTile gt = IDB_TILE_PACK;                         // tile index, K range and the seek's source: no kernel-argument load
     int wg, kz, tm, tn;
-    idb_wg_tile(p, wg, kz);
-    idb_tile_mn(p, wg, tm, tn);
+    idb_wg_tile(gt, wg, kz);
+    idb_tile_mn(gt, wg, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     // this workgroup's K range in K-steps of the chunk-major walk (balanced; a split may start and end inside a chunk)
     int g0, g1;
-    idb_k_range(p, kz, g0, g1);
+    idb_k_range(gt, kz, g0, g1);
     const int nk = g1 - g0;
     int s0, c0, t0, base0;
-    idb_patch_seek(p, g0, s0, c0, t0, base0);
+    idb_patch_seek(gt, p, g0, s0, c0, t0, base0);
     // tile geometry: R image rows of width W; nimg whole images when the image is smaller than the tile
     // (resolved on the host for this variant's BM: idb_fill_geometry)
     const int W = p.OW, H = p.pc_H;
@@ -792,7 +807,7 @@ __global__ __launch_bounds__(GN ? 896 : 768) void idb_conv_patch_kernel(const Ge
 //   raw inputs of a fused 1x1 shortcut) pass untouched.  A tile lies inside one sample, or covers whole samples (host check).
 // ------------------------------------------------------------------------------------------------------------
 template <typename T, int MF, int NF, int NS, int WM, int NV>
-__global__ __launch_bounds__(128 * WM + 256 + 64 * NV) void idb_gemm_kernel_gn(const GemmParams p) {
+__global__ __launch_bounds__(128 * WM + 256 + 64 * NV) void idb_gemm_kernel_gn(IDB_TILE_PARAMS, const GemmParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using V8 = typename Op<T>::v8;
     constexpr int LW = 4;
@@ -813,17 +828,19 @@ __global__ __launch_bounds__(128 * WM + 256 + 64 * NV) void idb_gemm_kernel_gn(c
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
+    const GemmTile h = IDB_TILE_PACK;                          // tile index, K range and the seek's source: no kernel-argument load
     int wg, kz, tm, tn;
-    idb_wg_tile(p, wg, kz);
-    idb_tile_mn(p, wg, tm, tn);
+    idb_wg_tile(h, wg, kz);
+    idb_tile_mn(h, wg, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     int kt0, kt1;
-    idb_k_range(p, kz, kt0, kt1);
+    idb_k_range(h, kz, kt0, kt1);
     const int nk = kt1 - kt0;
 
     // K-step cursor shared by loaders and normalizers: source s, tap, channel offset c0
-    int s, tap, c0;
-    idb_k_seek(p, kt0, s, tap, c0);
+    int s, rem, tap, c0;
+    idb_k_seek_src(h, kt0, s, rem);
+    idb_k_seek_tap(p.src[s], rem, tap, c0);
     auto advance = [&]() {                                     // to the next K-step
         c0 += 64;
         if (c0 == p.src[s].C) {
@@ -1506,12 +1523,29 @@ size_t gn_fused_lds(const Variant& v, long long hw, long long cn, int groups) {
     return (size_t)v.gn_lds + (size_t)(nsamp * cn * 8) + (size_t)(nsamp * groups * 8);
 }
 
+// Launch of a kernel whose launch scalars stand in front of GemmParams as plain parameters (GemmTile, idb_gemm_epi.h)
+template <auto K>
+static int idb_launch_tile(const char* api, const char* name, dim3 grid, dim3 block, size_t lds, int lds_max, hipStream_t st, const GemmParams& p, int tiles) {
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        if (e != hipSuccess) {
+            idb_set_error("%s: hipFuncSetAttribute(%d) failed: %s", api, lds_max, hipGetErrorString(e));
+            return IDB_EHIP;
+        }
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(K, grid, block, lds, st, IDB_TILE_ARGS(p, tiles), p);
+    IDB_CHECK_LAUNCH(name);
+    return IDB_OK;
+}
+
 template <typename T, Family F, int MF, int NF, int NS, int WM, int LW, bool GN, bool RELU = false>
 int launch_variant(const Variant& v, const GemmParams& p, const Plan& pl, hipStream_t st) {
     const int tiles = pl.tiles_m * pl.tiles_n;
     const dim3 grid(tiles, 1, pl.splitk);
     if constexpr (GN && F == kPatchSmall) {
-        return idb_launch<idb_conv_patch_kernel<T, MF, NF, NS, true>>("idb_gemm", "idb_gemm(patch)", grid, dim3(896), v.gn_lds, v.gn_lds, st, p);
+        return idb_launch_tile<idb_conv_patch_kernel<T, MF, NF, NS, true>>("idb_gemm", "idb_gemm(patch)", grid, dim3(896), v.gn_lds, v.gn_lds, st, p, tiles);
     } else if constexpr (GN) {
         // 4 MFMA waves (2 x 2, one per SIMD: the wave tile is twice that of the 8-wave kernels of the same workgroup tile) + 4 loader waves +
         // 8 normalizer waves = 16 waves: with 4 normalizer waves the transform (9x redundant for a 3x3 conv: every tap re-reads its pixels)
@@ -1522,21 +1556,21 @@ int launch_variant(const Variant& v, const GemmParams& p, const Plan& pl, hipStr
             idb_set_error("idb_gemm: fused GroupNorm needs %zu bytes of LDS for this tile", lds);
             return IDB_EUNSUPPORTED;
         }
-        return idb_launch<idb_gemm_kernel_gn<T, 2, NF, 4, 2, 8>>("idb_gemm", "idb_gemm(gn)", grid, dim3(128 * 2 + 256 + 64 * 8), lds, 160 * 1024, st, p);
+        return idb_launch_tile<idb_gemm_kernel_gn<T, 2, NF, 4, 2, 8>>("idb_gemm", "idb_gemm(gn)", grid, dim3(128 * 2 + 256 + 64 * 8), lds, 160 * 1024, st, p, tiles);
     } else if constexpr (F <= kRing4 && RELU) {
-        return idb_launch<idb_gemm_kernel_relu<T, MF, NF, NS, WM>>("idb_gemm", "idb_gemm(relu)", grid, dim3(v.threads), v.lds, v.lds, st, p);
+        return idb_launch_tile<idb_gemm_kernel_relu<T, MF, NF, NS, WM>>("idb_gemm", "idb_gemm(relu)", grid, dim3(v.threads), v.lds, v.lds, st, p, tiles);
     } else if constexpr (F <= kRing4) {
-        return idb_launch<idb_gemm_kernel<T, MF, NF, NS, WM>>("idb_gemm", "idb_gemm", grid, dim3(v.threads), v.lds, v.lds, st, p);
+        return idb_launch_tile<idb_gemm_kernel<T, MF, NF, NS, WM>>("idb_gemm", "idb_gemm", grid, dim3(v.threads), v.lds, v.lds, st, p, tiles);
     } else if constexpr (F == kRegStaged) {
         return idb_launch<idb_gemm_kernel_rs<T, MF, NF>>("idb_gemm", "idb_gemm(rs)", grid, dim3(v.threads), v.lds, v.lds, st, p);
     } else if constexpr (F == kPersistent) {
         return idb_launch<idb_gemm_kernel_pl<T, MF, NF>>("idb_gemm", "idb_gemm(pl)", dim3(tiles < 512 ? tiles : 512), dim3(v.threads), v.lds, v.lds, st, p);
     } else if constexpr (F <= kLw256 && RELU) {
-        return idb_launch<idb_gemm_kernel_lw_relu<T, MF, NF, NS, WM, LW>>("idb_gemm", "idb_gemm(lw, relu)", grid, dim3(v.threads), v.lds, v.lds, st, p);
+        return idb_launch_tile<idb_gemm_kernel_lw_relu<T, MF, NF, NS, WM, LW>>("idb_gemm", "idb_gemm(lw, relu)", grid, dim3(v.threads), v.lds, v.lds, st, p, tiles);
     } else if constexpr (F <= kLw256) {
-        return idb_launch<idb_gemm_kernel_lw<T, MF, NF, NS, WM, LW>>("idb_gemm", "idb_gemm(lw)", grid, dim3(v.threads), v.lds, v.lds, st, p);
+        return idb_launch_tile<idb_gemm_kernel_lw<T, MF, NF, NS, WM, LW>>("idb_gemm", "idb_gemm(lw)", grid, dim3(v.threads), v.lds, v.lds, st, p, tiles);
     } else {
-        return idb_launch<idb_conv_patch_kernel<T, MF, NF, NS>>("idb_gemm", "idb_gemm(patch)", grid, dim3(v.threads), v.lds, v.lds, st, p);
+        return idb_launch_tile<idb_conv_patch_kernel<T, MF, NF, NS>>("idb_gemm", "idb_gemm(patch)", grid, dim3(v.threads), v.lds, v.lds, st, p, tiles);
     }
 }
 

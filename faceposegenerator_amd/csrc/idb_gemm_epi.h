@@ -5,38 +5,56 @@
 #include "idb_fastdiv.h"
 #include <stdlib.h>
 
-struct GemmSrcK {
+// One 64-byte record per source: a loader fetches the record of its first K-step as ONE 16-dword scalar load.
+struct alignas(64) GemmSrcK {
     const char* ptr;
     unsigned bytes;   // tensor size in bytes = buffer num_records (< 2^31, checked on the host)
     int C, taps, H, W, up;
     int steps;            // K-steps of this source = taps * (C / 64): what the K seeks subtract        } idb_fill_geometry
     idb_fastdiv fd_cs;    // division by C / 64 (numerator < 9 C / 64: the tap of a K-step)            }
+    unsigned rsv[4];
 };
+static_assert(sizeof(GemmSrcK) == 64, "one source record = one 16-dword scalar load");
 
 // The launch geometry is resolved ONCE, on the host (idb_fill_geometry): every quotient a kernel prologue or epilogue needs whose
 // divisor is fixed by the launch comes in as a value (H, nimg, RI, cpg, ...), or as an idb_fastdiv record (idb_fastdiv.h: multiply-high
 // by an exact reciprocal, or a shift).  The kernels hold no division by a run-time value in front of their first load: each was
 // 25-40 instructions (100+ for the 64-bit K ranges), recomputed by every workgroup of every launch — 7-12 of them on the loader
 // waves' path to the first LDS-DMA.
-// Layout: the scalars a loader wave reads before its first DMA stand together at the head (kernel arguments arrive through scalar
-// loads of up to 16 consecutive dwords: neighbours share a load and its wait), the sources behind them, the epilogue's operands last.
-struct GemmParams {
-    // ---- tile and K range of the workgroup, row decode, weight addressing
+//
+// Kernel arguments arrive through scalar loads, and a wave that reads them where it first uses them — role by role, behind branches,
+// the source record behind the K seek that names it — stands through one kernel-argument round trip after the other before its first
+// load is in flight.  So the arguments are laid out by WHEN they are needed:
+//   * GemmTile — what the tile index, the K range and the K seek's source need (14 dwords): LEADING PLAIN kernel parameters of the
+//     ring / loader-wave / patch / fused-GroupNorm kernels, in front of the struct.  With the Makefile's KERNARG_PRELOAD flag the
+//     hardware puts them into SGPRs at wave launch: that arithmetic waits for no load at all.
+//   * GemmHead — row decode, weight addressing, grouped weights: the first 128 bytes of GemmParams = two 16-dword scalar loads
+//     (the struct is 64-byte aligned in the kernel-argument segment).
+//   * src[] — one 64-byte record each.  The record of the first K-step is named by GemmTile alone, so its load is issued together
+//     with the head's: idb_loader_head requests all three and holds ONE wait in front of the first DMA.
+//   * everything else (patch geometry, fused GroupNorm, the epilogue's operands) behind them, read where it is used.
+struct alignas(64) GemmHead {
+    // ---- 16 dwords: row decode, weight addressing
     int M, N, HW, OW, stride, pad;
-    int tiles_n, ktiles, splitk;
-    int xcd_mode;   // 0: tiles dealt to XCDs in runs, K-split on grid z; 1/2: one K-slice per XCD (group), see idb_gemm_kernel
-    idb_fastdiv fd_tiles_n;          // tile index / tiles_n
-    idb_fastdiv fd_splitk;           // kz * ktiles / splitk: the K ranges stay floor(kz ktiles / splitk) .. floor((kz + 1) ktiles / splitk)
-    idb_fastdiv fd_gx;               // xcd_mode 1: (linear id >> 3) / gridDim.x
     idb_fastdiv fd_hw, fd_ow;        // m / HW, (m % HW) / OW
     unsigned w_row_bytes, w_bytes;   // w_row_bytes: bytes between consecutive weight rows inside a 16-row block
     unsigned w_blk_bytes, w_kstep;   // bytes between 16-row blocks / between K-steps of one row (idb_gemm_desc.w_layout; idb_gemm kernels only)
+    // ---- 16 dwords: the weight matrix of the tile; the tile / K-range scalars for the kernels that take no GemmTile
     const char* w;
     // grouped weights (idb_gemm_desc.w_groups): tile rows [m0, m0 + BM) use matrix (m0 / w_group_rows) % w_groups
-    int w_groups, w_group_rows;
     long long w_group_stride;
+    int w_groups, w_group_rows;
     idb_fastdiv fd_wgr, fd_wg;       // m0 / w_group_rows, that / w_groups
+    int tiles_n, ktiles, splitk;
+    int xcd_mode;   // 0: tiles dealt to XCDs in runs, K-split on grid z; 1/2: one K-slice per XCD (group), see idb_gemm_kernel
+};
+static_assert(sizeof(GemmHead) == 128, "the head = two 16-dword scalar loads");
+
+struct GemmParams : GemmHead {
     GemmSrcK src[IDB_MAX_SRC];
+    idb_fastdiv fd_tiles_n;          // tile index / tiles_n
+    idb_fastdiv fd_splitk;           // kz * ktiles / splitk: the K ranges stay floor(kz ktiles / splitk) .. floor((kz + 1) ktiles / splitk)
+    idb_fastdiv fd_gx;               // xcd_mode 1: (linear id >> 3) / gridDim.x
     // ---- patch-resident conv (idb_conv_patch_kernel), for the variant's row tile: image height, whole images per tile (1 when the
     // image is larger than the tile), tile rows per image; divisions by the patch width OW + 2h and by RI + 2h (h = 1: 3x3 halo)
     int pc_H, pc_nimg, pc_RI;
@@ -103,6 +121,7 @@ inline bool idb_fill_geometry(GemmParams& p, long long tiles, int bm) {
     for (int s = 0; s < IDB_MAX_SRC; ++s) {
         const int cs = p.src[s].C >> 6;
         p.src[s].steps = p.src[s].taps * cs;
+        ok &= p.src[s].steps >= 0 && p.src[s].steps < 65536;                   // GemmTile carries them as 16-bit fields
         p.src[s].fd_cs = idb_fastdiv_make(cs > 0 ? (uint32_t)cs : 1u, (uint32_t)(9 * (cs > 0 ? cs : 1)), &k), ok &= k;
     }
     p.pc_H = p.HW / p.OW;
@@ -127,6 +146,30 @@ inline bool idb_fill_geometry(GemmParams& p, long long tiles, int bm) {
     p.fd_swc = idb_fastdiv_make((uint32_t)swc, 0x7FFFFFFFu, &k), ok &= k;
     return ok;
 }
+
+// ---- GemmTile: the launch scalars that stand in front of the struct as plain kernel parameters (see GemmParams) -----------------
+// 14 dwords = what a kernel-argument preload holds beside the segment pointer, in the order the prologue reads them: the XCD remap
+// and tile index, the K range, the step counts of sources 0..2 that the K seek walks (16 bits each, host-checked).
+static_assert(IDB_MAX_SRC == 4, "GemmTile carries the step counts of sources 0..2: the K seeks stop at the last source");
+struct GemmTile {
+    int mode_st2;                    // xcd_mode << 16 | src[2].steps
+    int tiles;                       // workgroups per K slice = gridDim.x
+    idb_fastdiv fd_tiles_n;
+    int tiles_n, ktiles;
+    idb_fastdiv fd_splitk;
+    int st01;                        // src[1].steps << 16 | src[0].steps
+    idb_fastdiv fd_gx;
+};
+#define IDB_TILE_PARAMS                                                                                                                         \
+    int t_mode_st2, int t_tiles, unsigned t_tn_mul, unsigned t_tn_add, unsigned t_tn_sh, int t_tiles_n, int t_ktiles, unsigned t_sk_mul,        \
+        unsigned t_sk_add, unsigned t_sk_sh, int t_st01, unsigned t_gx_mul, unsigned t_gx_add, unsigned t_gx_sh
+#define IDB_TILE_PACK                                                                                                                           \
+    GemmTile { t_mode_st2, t_tiles, {t_tn_mul, t_tn_add, t_tn_sh}, t_tiles_n, t_ktiles, {t_sk_mul, t_sk_add, t_sk_sh}, t_st01, {t_gx_mul, t_gx_add, t_gx_sh} }
+// host: the same fourteen values out of a filled GemmParams, for a grid of `tiles` workgroups per K slice
+#define IDB_TILE_ARGS(p, tiles)                                                                                                                 \
+    (int)(((unsigned)(p).xcd_mode << 16) | (unsigned)(p).src[2].steps), (int)(tiles), (p).fd_tiles_n.mul, (p).fd_tiles_n.add, (p).fd_tiles_n.sh,  \
+        (p).tiles_n, (p).ktiles, (p).fd_splitk.mul, (p).fd_splitk.add, (p).fd_splitk.sh,                                                        \
+        (int)(((unsigned)(p).src[1].steps << 16) | (unsigned)(p).src[0].steps), (p).fd_gx.mul, (p).fd_gx.add, (p).fd_gx.sh
 
 // ---- device side of the resolved geometry (shared by every implicit-GEMM kernel) -------------------------------------------
 // workgroup -> output tile wg and K slice kz: the XCD-aware bijective remaps described at idb_gemm_kernel
@@ -165,6 +208,83 @@ __device__ __forceinline__ void idb_k_range(const GemmParams& p, int kz, int& kt
     kt1 = idb_fd_div(a + p.ktiles, p.fd_splitk);
 }
 
+// The same three for the kernels whose launch scalars are plain parameters (GemmTile): no kernel-argument load in front of them.
+__device__ __forceinline__ void idb_wg_tile(const GemmTile& h, int& wg, int& kz) {
+    const int mode = (int)((unsigned)h.mode_st2 >> 16);
+    if (mode == 0) {
+        const int nwg = h.tiles, orig = blockIdx.x;
+        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
+        wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+        kz = blockIdx.z;
+    } else {
+        const int X = h.tiles;
+        const int lin = blockIdx.x + X * blockIdx.z;
+        const int xcd = lin & 7, j = lin >> 3;
+        if (mode == 1) {
+            const int jq = idb_fd_div(j, h.fd_gx);
+            kz = xcd + 8 * jq;
+            wg = j - jq * X;
+        } else {
+            kz = xcd >> 1;
+            wg = (xcd & 1) * (X >> 1) + j;
+        }
+    }
+}
+
+__device__ __forceinline__ void idb_tile_mn(const GemmTile& h, int wg, int& tm, int& tn) {
+    tm = idb_fd_div(wg, h.fd_tiles_n);
+    tn = wg - tm * h.tiles_n;
+}
+
+__device__ __forceinline__ void idb_k_range(const GemmTile& h, int kz, int& kt0, int& kt1) {
+    const int a = kz * h.ktiles;
+    kt0 = idb_fd_div(a, h.fd_splitk);
+    kt1 = idb_fd_div(a + h.ktiles, h.fd_splitk);
+}
+
+// K seek, first half: the source s of K-step kt and the K-step inside it, from the step counts GemmTile carries — no load, so the
+// source record's address is known before any kernel argument has been waited for.
+__device__ __forceinline__ void idb_k_seek_src(const GemmTile& h, int kt, int& s, int& rem) {
+    const int st[IDB_MAX_SRC - 1] = {h.st01 & 0xffff, (int)((unsigned)h.st01 >> 16), h.mode_st2 & 0xffff};
+    rem = kt;
+    s = 0;
+#pragma unroll
+    for (int q = 0; q < IDB_MAX_SRC - 1; ++q) {
+        if (s == q && rem >= st[q]) {
+            rem -= st[q];
+            ++s;
+        }
+    }
+}
+
+// second half: tap and channel offset inside source record S (a 1x1 source sits on the centre tap 4)
+__device__ __forceinline__ void idb_k_seek_tap(const GemmSrcK& S, int rem, int& tap, int& c0) {
+    if (S.taps == 9) {
+        tap = idb_fd_div(rem, S.fd_cs);
+        c0 = (rem - tap * (S.C >> 6)) << 6;
+    } else {
+        tap = 4;
+        c0 = rem << 6;
+    }
+}
+
+// What a loader wave needs in front of its first DMA beside GemmTile: the head and the source record of its first K-step, as three
+// 16-dword scalar loads requested together.  The empty asm reads all three as scalar-register operands right here: the loads cannot be
+// sunk towards their first uses behind later branches, and the first use of any of them waits for all (scalar loads return out of order).
+typedef unsigned idb_u32x16 __attribute__((ext_vector_type(16)));
+struct GemmHeadRaw {
+    idb_u32x16 a, b;
+};
+__device__ __forceinline__ void idb_loader_head(const GemmParams& p, int s, GemmHead& hd, GemmSrcK& S) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const GemmHeadRaw r = __builtin_bit_cast(GemmHeadRaw, static_cast<const GemmHead&>(p));
+    const idb_u32x16 c = __builtin_bit_cast(idb_u32x16, p.src[s]);
+    asm volatile("" ::"s"(r.a), "s"(r.b), "s"(c));
+    hd = __builtin_bit_cast(GemmHead, r);
+    S = __builtin_bit_cast(GemmSrcK, c);
+#endif
+}
+
 // K-step kt of the tap-major K walk ([source][tap][channel chunk]) -> source s, tap (a 1x1 source sits on the centre tap 4), channel offset c0
 __device__ __forceinline__ void idb_k_seek(const GemmParams& p, int kt, int& s, int& tap, int& c0) {
     int rem = kt;
@@ -185,7 +305,7 @@ __device__ __forceinline__ void idb_k_seek(const GemmParams& p, int kt, int& s, 
 }
 
 // output row m -> (sample, y, x); HW == 1 (a plain [M][K] matrix) comes out as (m, 0, 0) through the same shifts
-__device__ __forceinline__ void idb_row_decode(const GemmParams& p, int m, int& b, int& oy, int& ox) {
+__device__ __forceinline__ void idb_row_decode(const GemmHead& p, int m, int& b, int& oy, int& ox) {
     b = idb_fd_div(m, p.fd_hw);
     const int rem = m - b * p.HW;
     oy = idb_fd_div(rem, p.fd_ow);
@@ -193,7 +313,7 @@ __device__ __forceinline__ void idb_row_decode(const GemmParams& p, int m, int& 
 }
 
 // byte offset of the weight matrix (and element offset of its folded-LayerNorm vectors) a tile uses
-__device__ __forceinline__ int idb_weight_group(const GemmParams& p, int m0) {
+__device__ __forceinline__ int idb_weight_group(const GemmHead& p, int m0) {
     if (p.w_groups <= 1) return 0;
     const int q = idb_fd_div(m0, p.fd_wgr);
     return q - idb_fd_div(q, p.fd_wg) * p.w_groups;

@@ -23,14 +23,27 @@
     //          tile, so every weight and activation byte crosses the fabric once instead of once per XCD — on the batch-1
     //          weight-streaming layers (M = 512: 4 row tiles on 4 XCD pairs) mode 0 fetched the weights 4-8 times
     //          (rocprofv3 FETCH_SIZE: 99-113 MB per launch against 28-40 MB of operands).
+    // `h` (GemmTile) holds the launch scalars as plain kernel parameters: tile index, K range and the source of the first K-step need no
+    // kernel-argument load.  The head and that source's record are then requested together and waited for once (idb_loader_head).
     int wg, kz, tm, tn;
-    idb_wg_tile(p, wg, kz);
-    idb_tile_mn(p, wg, tm, tn);
+    idb_wg_tile(h, wg, kz);
+    idb_tile_mn(h, wg, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
 
     int kt0, kt1;                                            // balanced partition: slice sizes differ by at most one
-    idb_k_range(p, kz, kt0, kt1);
+    idb_k_range(h, kz, kt0, kt1);
     const int nk = kt1 - kt0;
+
+    // ---- K-step state: source s, tap (0..8; a 1x1 source sits on the centre tap 4), channel offset c0.
+    // Per-row voffsets (pixel address, zero padding -> out-of-range) are recomputed only when the tap or the
+    // source changes (every C/64 K-steps); inside a tap the channel offset rides in the SGPR soffset, so a
+    // K-step costs no address VALU at all.
+    int s, rem, tap, c0, cur_c = 64, tap_end = 9;
+    idb_k_seek_src(h, kt0, s, rem);
+    GemmHead q;
+    GemmSrcK S;
+    idb_loader_head(p, s, q, S);
+    idb_k_seek_tap(S, rem, tap, c0);
 
     // ---- per-thread staging coordinates: thread loads chunk position (tid&7) of rows (tid>>3)+32i;
     // the 16-byte chunk it fetches is (tid&7) ^ (row&7): the swizzle lives on the source address.
@@ -41,47 +54,30 @@
 #pragma unroll
     for (int i = 0; i < MF; ++i) {
         const int m = m0 + i * RS + lrow;
-        a_ok[i] = m < p.M;
-        idb_row_decode(p, a_ok[i] ? m : 0, a_b[i], a_oy[i], a_ox[i]);
+        a_ok[i] = m < q.M;
+        idb_row_decode(q, a_ok[i] ? m : 0, a_b[i], a_oy[i], a_ox[i]);
     }
-    // weights: one descriptor, per-row voffset fixed for the whole K loop, K position in the SGPR soffset
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w + idb_weight_group(p, m0) * p.w_group_stride), 0, p.w_bytes, IDB_RSRC_FLAGS);
-    unsigned w_voff[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int n = n0 + j * RS + lrow;
-        w_voff[j] = (n < p.N && j * RS + lrow < BN) ? (unsigned)(n >> 4) * p.w_blk_bytes + (unsigned)(n & 15) * p.w_row_bytes + cg16 : IDB_OOB;
-    }
-    unsigned w_soff = (unsigned)kt0 * p.w_kstep;
-
-    // ---- K-step state: source s, tap (0..8; a 1x1 source sits on the centre tap 4), channel offset c0.
-    // Per-row voffsets (pixel address, zero padding -> out-of-range) are recomputed only when the tap or the
-    // source changes (every C/64 K-steps); inside a tap the channel offset rides in the SGPR soffset, so a
-    // K-step costs no address VALU at all.
-    int s, tap, c0, cur_c = 64, tap_end = 9;
-    idb_k_seek(p, kt0, s, tap, c0);
-    __amdgpu_buffer_rsrc_t rs_a = rs_w;
-    unsigned a_voff[MF];
+    __amdgpu_buffer_rsrc_t rs_a, rs_w;
+    unsigned a_voff[MF], w_voff[NJ];
+    unsigned w_soff = (unsigned)kt0 * q.w_kstep;
     bool need_retap = true;
     auto retap = [&]() {
-        const GemmSrcK S = p.src[s];
         rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)S.ptr, 0, S.bytes, IDB_RSRC_FLAGS);
         cur_c = S.C;
         tap_end = S.taps == 9 ? 9 : 5;
         const int t3 = tap / 3;
-        const int dy = t3 - p.pad, dx = tap - t3 * 3 - p.pad;
+        const int dy = t3 - q.pad, dx = tap - t3 * 3 - q.pad;
         const int LH = S.H << S.up, LW = S.W << S.up;
 #pragma unroll
         for (int i = 0; i < MF; ++i) {
-            const int iy = a_oy[i] * p.stride + dy, ix = a_ox[i] * p.stride + dx;
+            const int iy = a_oy[i] * q.stride + dy, ix = a_ox[i] * q.stride + dx;
             const bool ok = a_ok[i] && (unsigned)iy < (unsigned)LH && (unsigned)ix < (unsigned)LW;
             const int pix = (a_b[i] * S.H + (iy >> S.up)) * S.W + (ix >> S.up);
             a_voff[i] = ok ? (unsigned)pix * (unsigned)(S.C * 2) + cg16 : IDB_OOB;
         }
     };
-    auto stage = [&](int buf) {
+    auto stage_a = [&](int buf) {                            // the A half of a stage
         char* sA = smem + buf * STAGE;
-        char* sB = sA + BM * 128;
         if (need_retap) {
             retap();
             need_retap = false;
@@ -90,20 +86,39 @@
 #pragma unroll
         for (int i = 0; i < MF; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, LDS_PTR(sA + (i * THREADS + wave * 64) * 16), 16, a_voff[i], a_soff, 0, 0);
+    };
+    auto stage_w = [&](int buf) {                            // the W half, and on to the next K-step
+        char* sB = smem + buf * STAGE + BM * 128;
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, LDS_PTR(sB + (j * THREADS + wave * 64) * 16), 16, w_voff[j], w_soff, 0, 0);
-        w_soff += p.w_kstep;
+        w_soff += q.w_kstep;
         c0 += 64;
         if (c0 == cur_c) {
             c0 = 0;
             need_retap = true;
             if (++tap == tap_end) {
-                if (s < IDB_MAX_SRC - 1) ++s;
-                tap = p.src[s].taps == 9 ? 0 : 4;
+                if (s < IDB_MAX_SRC - 1) S = p.src[++s];
+                tap = S.taps == 9 ? 0 : 4;
             }
         }
     };
+    auto stage = [&](int buf) {
+        stage_a(buf);
+        stage_w(buf);
+    };
+    // First DMA first, as in idb_gemm_kernel_lw: the A half of stage 0 is requested as soon as the K seek and the row decode allow;
+    // the weight descriptor, the weight offsets and the grouped-weight arithmetic — which only the W half needs — come behind it.
+    // The loads of a stage keep their order and count.
+    if (0 < nk) stage_a(0);
+    // weights: one descriptor, per-row voffset fixed for the whole K loop, K position in the SGPR soffset
+    rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)(q.w + idb_weight_group(q, m0) * q.w_group_stride), 0, q.w_bytes, IDB_RSRC_FLAGS);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int n = n0 + j * RS + lrow;
+        w_voff[j] = (n < q.N && j * RS + lrow < BN) ? (unsigned)(n >> 4) * q.w_blk_bytes + (unsigned)(n & 15) * q.w_row_bytes + cg16 : IDB_OOB;
+    }
+    if (0 < nk) stage_w(0);
 
     f32x4 acc[MF][NF];
 #pragma unroll
@@ -116,7 +131,7 @@
     // visible AND proves that all waves are done reading tile it-1, whose buffer the next DMA overwrites.
     constexpr int LOADS = MF + NJ;
 #pragma unroll
-    for (int st = 0; st < NS - 1; ++st)
+    for (int st = 1; st < NS - 1; ++st)
         if (st < nk) stage(st);
     // folded LayerNorm: this thread's share of its tile row's statistics, the loads in flight with the first operand tiles
     float2 ln_part = make_float2(0.f, 0.f);
