@@ -388,6 +388,14 @@ __global__ __launch_bounds__(256) void embed_kernel(const long long* __restrict_
 
 inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 
+// blocks_for returns unsigned and a grid's x extent stays below 2^31: one call covers fewer than 2^31 * 256 = 2^39 elements.  The product
+// of up to three positive sizes is taken in 128 bits (three int32 sizes, or two int64 ones, overflow a long long).
+inline bool below_2p39(long long a, long long b = 1, long long c = 1) {
+    const long long lim = 1LL << 39;
+    if (a <= 0 || b <= 0 || c <= 0 || a >= lim || b >= lim || c >= lim) return false;
+    return (unsigned __int128)a * (unsigned __int128)b * (unsigned __int128)c < (unsigned __int128)lim;
+}
+
 }  // namespace
 
 #define DISPATCH_T(dtype, CALL_BF16, CALL_F16) \
@@ -436,6 +444,7 @@ extern "C" int idb_cfg_ddpm_step(const float* eps, float* latents, const float* 
                                  void* stream) {
     IDB_REQUIRE(eps && latents && coef && batch > 0 && channels > 0 && hw > 0, "idb_cfg_ddpm_step: bad args");
     IDB_REQUIRE(prediction_type == 0 || prediction_type == 1, "idb_cfg_ddpm_step: prediction_type must be 0 (epsilon) or 1 (v)");
+    IDB_REQUIRE(below_2p39(batch, channels, hw), "idb_cfg_ddpm_step: 2^39 or more elements");
     hipLaunchKernelGGL(cfg_ddpm_kernel, dim3(blocks_for((long long)batch * channels * hw)), dim3(256), 0, (hipStream_t)stream,
                        eps, latents, noise, coef, x0_out, batch, channels, hw, cfg, prediction_type);
     IDB_CHECK_LAUNCH("idb_cfg_ddpm_step");
@@ -456,6 +465,7 @@ extern "C" int idb_warp_affine_u8(const uint8_t* src, int32_t batch, int32_t h, 
 extern "C" int idb_vae_sample(const float* moments, const float* noise, float scale, float* latents, float* mean_out,
                               float* logvar_out, int32_t batch, int32_t channels, int32_t hw, void* stream) {
     IDB_REQUIRE(moments && latents && batch > 0 && channels > 0 && hw > 0, "idb_vae_sample: bad args");
+    IDB_REQUIRE(below_2p39(batch, channels, hw) && channels < (1 << 30), "idb_vae_sample: 2^39 or more elements, or 2^30 or more channels");
     hipLaunchKernelGGL(vae_sample_kernel, dim3(blocks_for((long long)batch * channels * hw)), dim3(256), 0, (hipStream_t)stream,
                        moments, noise, scale, latents, mean_out, logvar_out, batch, channels, hw);
     IDB_CHECK_LAUNCH("idb_vae_sample");
@@ -464,6 +474,7 @@ extern "C" int idb_vae_sample(const float* moments, const float* noise, float sc
 
 extern "C" int idb_postprocess(const float* x, float* img01, uint8_t* u8, int64_t count, void* stream) {
     IDB_REQUIRE(x && (img01 || u8) && count > 0, "idb_postprocess: bad args");
+    IDB_REQUIRE(below_2p39(count), "idb_postprocess: 2^39 or more elements");
     hipLaunchKernelGGL(postprocess_kernel, dim3(blocks_for(count)), dim3(256), 0, (hipStream_t)stream, x, img01, u8,
                        (long long)count);
     IDB_CHECK_LAUNCH("idb_postprocess");
@@ -473,6 +484,7 @@ extern "C" int idb_postprocess(const float* x, float* img01, uint8_t* u8, int64_
 extern "C" int idb_nhwc_to_nchw_f32(const void* x, float* out, int32_t batch, int32_t hw, int32_t c, int32_t dtype,
                                     void* stream) {
     IDB_REQUIRE(idb_is_operand_dtype(dtype) && x && out && batch > 0 && hw > 0 && c > 0, "idb_nhwc_to_nchw_f32: bad args");
+    IDB_REQUIRE(below_2p39(batch, hw, c), "idb_nhwc_to_nchw_f32: 2^39 or more elements");
     const unsigned nb = blocks_for((long long)batch * hw * c);
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype, hipLaunchKernelGGL((nhwc_to_nchw_kernel<__bf16>), dim3(nb), dim3(256), 0, st, (const __bf16*)x, out, batch, hw, c),
@@ -483,6 +495,7 @@ extern "C" int idb_nhwc_to_nchw_f32(const void* x, float* out, int32_t batch, in
 
 extern "C" int idb_f32_nhwc_to_nchw(const float* x, float* out, int32_t batch, int32_t hw, int32_t c, void* stream) {
     IDB_REQUIRE(x && out && batch > 0 && hw > 0 && c > 0, "idb_f32_nhwc_to_nchw: bad args");
+    IDB_REQUIRE(below_2p39(batch, hw, c), "idb_f32_nhwc_to_nchw: 2^39 or more elements");
     hipLaunchKernelGGL((nhwc_to_nchw_kernel<float>), dim3(blocks_for((long long)batch * hw * c)), dim3(256), 0,
                        (hipStream_t)stream, x, out, batch, hw, c);
     IDB_CHECK_LAUNCH("idb_f32_nhwc_to_nchw");
@@ -491,6 +504,7 @@ extern "C" int idb_f32_nhwc_to_nchw(const float* x, float* out, int32_t batch, i
 
 extern "C" int idb_cast_f32(const float* x, void* out, int64_t count, int32_t dtype, void* stream) {
     IDB_REQUIRE(idb_is_operand_dtype(dtype) && x && out && count > 0, "idb_cast_f32: bad args");
+    IDB_REQUIRE(below_2p39(count), "idb_cast_f32: 2^39 or more elements");
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype, hipLaunchKernelGGL((cast_kernel<__bf16>), dim3(blocks_for(count)), dim3(256), 0, st, x, (__bf16*)out, (long long)count),
                hipLaunchKernelGGL((cast_kernel<_Float16>), dim3(blocks_for(count)), dim3(256), 0, st, x, (_Float16*)out, (long long)count));
@@ -503,6 +517,8 @@ extern "C" int idb_embed_tokens(const int64_t* ids, const float* tok, const floa
     IDB_REQUIRE(idb_is_operand_dtype(dtype) && ids && tok && pos && out, "idb_embed_tokens: bad args");
     IDB_REQUIRE(batch > 0 && n_tokens > 0 && dim > 0 && dim % 4 == 0 && idb_aligned16(tok) && idb_aligned16(pos) && idb_aligned16(out),
                 "idb_embed_tokens: dims/alignment");
+    IDB_REQUIRE(below_2p39(batch, n_tokens, dim) && (long long)batch * n_tokens < (1LL << 31),
+                "idb_embed_tokens: 2^39 or more elements, or 2^31 or more rows");
     const int rows = batch * n_tokens;
     const unsigned nb = blocks_for((long long)rows * (dim / 4));
     hipStream_t st = (hipStream_t)stream;
@@ -515,6 +531,7 @@ extern "C" int idb_embed_tokens(const int64_t* ids, const float* tok, const floa
 extern "C" int idb_pack_conv_weight(const float* src, void* dst, int32_t cout, int32_t cin, int32_t ktaps, int32_t dtype,
                                     void* stream) {
     IDB_REQUIRE(idb_is_operand_dtype(dtype) && src && dst && cout > 0 && cin > 0 && ktaps > 0, "idb_pack_conv_weight: bad args");
+    IDB_REQUIRE(below_2p39(cout, cin, ktaps), "idb_pack_conv_weight: 2^39 or more elements");
     const unsigned nb = blocks_for((long long)cout * cin * ktaps);
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype, hipLaunchKernelGGL((pack_conv_kernel<__bf16>), dim3(nb), dim3(256), 0, st, src, (__bf16*)dst, cout, cin, ktaps),
@@ -527,6 +544,7 @@ extern "C" int idb_pack_matrix(const float* src, void* dst, int64_t rows, int64_
                                void* stream) {
     IDB_REQUIRE(idb_is_operand_dtype(dtype) && src && dst && rows > 0 && cols > 0, "idb_pack_matrix: bad args");
     IDB_REQUIRE(!geglu || rows % 32 == 0, "idb_pack_matrix: GEGLU packing needs rows %% 32 == 0");
+    IDB_REQUIRE(below_2p39(rows, cols), "idb_pack_matrix: 2^39 or more elements");
     const unsigned nb = blocks_for(rows * cols);
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype, hipLaunchKernelGGL((pack_matrix_kernel<__bf16>), dim3(nb), dim3(256), 0, st, src, (__bf16*)dst, (long long)rows, (long long)cols, geglu),
@@ -539,6 +557,7 @@ extern "C" int idb_pack_matrix_scaled(const float* src, void* dst, int64_t rows,
                                       int32_t dtype, void* stream) {
     IDB_REQUIRE(idb_is_operand_dtype(dtype) && src && dst && col_scale && rows > 0 && cols > 0, "idb_pack_matrix_scaled: bad args");
     IDB_REQUIRE(!geglu || rows % 32 == 0, "idb_pack_matrix_scaled: GEGLU packing needs rows %% 32 == 0");
+    IDB_REQUIRE(below_2p39(rows, cols), "idb_pack_matrix_scaled: 2^39 or more elements");
     const unsigned nb = blocks_for(rows * cols);
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype, hipLaunchKernelGGL((pack_matrix_scaled_kernel<__bf16>), dim3(nb), dim3(256), 0, st, src, (__bf16*)dst, (long long)rows, (long long)cols, geglu, col_scale),
@@ -553,6 +572,7 @@ extern "C" int idb_ln_fold_vectors(const float* w, const float* lora_a, const fl
     IDB_REQUIRE(idb_is_operand_dtype(dtype) && w && w_folded && beta && u && v && rows > 0 && cols > 0 && rank >= 0 && rank <= 16 &&
                     (rank == 0 || !lora_a || lora_b), "idb_ln_fold_vectors: bad args");
     IDB_REQUIRE(!geglu || rows % 32 == 0, "idb_ln_fold_vectors: GEGLU row order needs rows %% 32 == 0");
+    IDB_REQUIRE(below_2p39(rows, cols) && rows < (1LL << 33), "idb_ln_fold_vectors: 2^39 or more elements, or 2^33 or more rows (four per workgroup)");
     const int rk = lora_a ? rank : 0;
     const unsigned nb = (unsigned)((rows + 3) / 4);
     hipStream_t st = (hipStream_t)stream;
@@ -567,6 +587,7 @@ extern "C" size_t idb_tiled_weight_bytes(int64_t n, int64_t k) { return n > 0 &&
 extern "C" int idb_tile_weight(const void* src, void* dst, int64_t n, int64_t k, int32_t dtype, void* stream) {
     IDB_REQUIRE(idb_is_operand_dtype(dtype) && src && dst && n > 0 && k > 0 && k % 64 == 0 && idb_aligned16(src) && idb_aligned16(dst),
                 "idb_tile_weight: needs operand dtype, 16-byte aligned pointers, k %% 64 == 0");
+    IDB_REQUIRE(n < (1LL << 39) && below_2p39((n + 15) / 16 * 16, k), "idb_tile_weight: 2^39 or more elements");
     const unsigned nb = blocks_for((n + 15) / 16 * (k / 64) * 128);
     hipLaunchKernelGGL(tile_weight_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const uint4*)src, (uint4*)dst, (long long)n, (long long)k);
     IDB_CHECK_LAUNCH("idb_tile_weight");
@@ -577,6 +598,7 @@ extern "C" int idb_lora_merge_scaled(const float* w, const float* lora_a, const 
                                      int32_t rank, float scale, const float* col_scale, int32_t dtype, void* stream) {
     IDB_REQUIRE(idb_is_operand_dtype(dtype) && w && dst && col_scale && rows > 0 && cols > 0 && rank >= 0 && ((lora_a && lora_b) || rank == 0),
                 "idb_lora_merge_scaled: bad args");
+    IDB_REQUIRE(below_2p39(rows, cols), "idb_lora_merge_scaled: 2^39 or more elements");
     const unsigned nb = blocks_for(rows * cols);
     hipStream_t st = (hipStream_t)stream;
     const int rk = lora_a ? rank : 0;
@@ -590,6 +612,7 @@ extern "C" int idb_lora_merge(const float* w, const float* lora_a, const float* 
                               int32_t rank, float scale, int32_t dtype, void* stream) {
     IDB_REQUIRE(idb_is_operand_dtype(dtype) && w && lora_a && lora_b && dst && rows > 0 && cols > 0 && rank > 0,
                 "idb_lora_merge: bad args");
+    IDB_REQUIRE(below_2p39(rows, cols), "idb_lora_merge: 2^39 or more elements");
     const unsigned nb = blocks_for(rows * cols);
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype, hipLaunchKernelGGL((lora_merge_kernel<__bf16>), dim3(nb), dim3(256), 0, st, w, lora_a, lora_b, (__bf16*)dst, (long long)rows, (long long)cols, rank, scale),

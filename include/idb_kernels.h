@@ -180,7 +180,17 @@ int32_t idb_gemm_folds_layernorm(const idb_gemm_desc* d);
 int32_t idb_gemm_fuses_groupnorm(const idb_gemm_desc* d);
 int idb_gemm(const idb_gemm_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
-/* Weight packing (run once at load; SURVEY.md §8b "idb_pack_*"). src is fp32 in torch layout. */
+/* Weight packing (run once at load; SURVEY.md §8b "idb_pack_*"). src is fp32 in torch layout.
+ * Limits of these entries and of the fp32 latent-path and boundary helpers below (idb_embed_tokens, idb_cfg_ddpm_step, idb_postprocess,
+ * idb_nhwc_to_nchw_f32, idb_f32_nhwc_to_nchw, idb_cast_f32, idb_vae_sample): every size positive and fewer than 2^39 elements per call
+ * (idb_tile_weight: of the padded destination), IDB_EINVAL before any HIP call; also idb_ln_fold_vectors rows < 2^33,
+ * idb_embed_tokens batch * n_tokens < 2^31 and idb_vae_sample channels < 2^30.  dst needs the element's own alignment only, except
+ * where 16 bytes are stated.
+ * Rounding.  idb_pack_conv_weight and idb_pack_matrix round each fp32 value once to the operand dtype (to nearest even).  Where a value
+ * is computed first (idb_pack_matrix_scaled, idb_lora_merge, idb_lora_merge_scaled), the last operation's result is rounded EITHER once
+ * to the operand dtype OR to fp32 and then to the operand dtype, as the compiler chose for that dtype (f16 has a fused
+ * multiply-add-and-convert, bf16 converts from an fp32 register): two values at most, which differ only where the fp32 rounding lands
+ * on a tie of the operand dtype.  tests/test_prep_matrix_gpu.py records which one each dtype produced. */
 /* [Cout][Cin][kh][kw] fp32 -> [Cout][kh*kw][Cin] operand dtype. */
 int idb_pack_conv_weight(const float* src, void* dst, int32_t cout, int32_t cin, int32_t ktaps,
                          int32_t dtype, void* stream);
@@ -195,11 +205,12 @@ int idb_tile_weight(const void* src, void* dst, int64_t n, int64_t k, int32_t dt
  * (peft lora.Linear with merged weights; inference_ID-Booth.py:107). */
 int idb_lora_merge(const float* w, const float* lora_a, const float* lora_b, void* dst, int64_t rows,
                    int64_t cols, int32_t rank, float scale, int32_t dtype, void* stream);
-/* The same with every column k multiplied by col_scale[k] before the one rounding (the gamma of a folded LayerNorm);
- * lora_a == NULL (rank 0): dst = round(W * col_scale). */
+/* The same with every column k multiplied by col_scale[k] before the rounding described above (the gamma of a folded LayerNorm);
+ * lora_a == NULL (rank 0): dst = round(W * col_scale), the exact product rounded once or through fp32. */
 int idb_lora_merge_scaled(const float* w, const float* lora_a, const float* lora_b, void* dst, int64_t rows, int64_t cols,
                           int32_t rank, float scale, const float* col_scale, int32_t dtype, void* stream);
-/* idb_pack_matrix with every column k multiplied by col_scale[k] before the one rounding (GEGLU projection behind a folded LayerNorm). */
+/* idb_pack_matrix with every column k multiplied by col_scale[k]: the exact product rounded once to the operand dtype, or to fp32 and
+ * then to it (see above) (GEGLU projection behind a folded LayerNorm). */
 int idb_pack_matrix_scaled(const float* src, void* dst, int64_t rows, int64_t cols, int32_t geglu, const float* col_scale,
                            int32_t dtype, void* stream);
 /* The two column vectors of a LayerNorm folded into a projection (idb_gemm_desc.ln_u / ln_v), for output rows r = 0..rows-1
@@ -335,12 +346,6 @@ int idb_f32_nhwc_to_nchw(const float* x, float* out, int32_t batch, int32_t hw, 
 /* [rows][cols] fp32 -> operand dtype (prompt embeddings). */
 int idb_cast_f32(const float* x, void* out, int64_t count, int32_t dtype, void* stream);
 
-/* ------------------------------------------------------------------------------------------
- * AutoencoderKL.encode tail (train_ID-Booth.py:1001-1002): DiagonalGaussianDistribution.sample()/.mode() times
- * vae.config.scaling_factor.  moments: fp32 [batch][hw][2*channels] (mean channels first, then log-variance), the
- * output of the encoder's conv_out with quant_conv folded in; noise: NCHW fp32 [batch][channels][hw] or NULL (mode);
- * latents, and optional mean / logvar (clamped to [-30, 20]) outputs: NCHW fp32.
- * ------------------------------------------------------------------------------------------ */
 /* ------------------------------------------------------------------------------------------
  * Face align-and-crop warp: cv2.warpAffine(img, M, (out_w, out_h), borderValue) for 8-bit images with
  * OpenCV's defaults (INTER_LINEAR, BORDER_CONSTANT) — utils/detect_align_crop_data.py:180.  src: uint8 [batch][h][w][channels];
@@ -614,6 +619,12 @@ int idb_resize_linear_u8(const void* src, int32_t batch, int32_t h, int32_t w, c
 int idb_fiqa_tail(const float* emb, const float* weight, const float* bias, int32_t batch, int32_t d, float* qs, float* emb_norm,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * AutoencoderKL.encode tail (train_ID-Booth.py:1001-1002): DiagonalGaussianDistribution.sample()/.mode() times
+ * vae.config.scaling_factor.  moments: fp32 [batch][hw][2*channels] (mean channels first, then log-variance), the
+ * output of the encoder's conv_out with quant_conv folded in; noise: NCHW fp32 [batch][channels][hw] or NULL (mode);
+ * latents, and optional mean / logvar (clamped to [-30, 20]) outputs: NCHW fp32.
+ * ------------------------------------------------------------------------------------------ */
 int idb_vae_sample(const float* moments, const float* noise, float scale, float* latents, float* mean_out,
                    float* logvar_out, int32_t batch, int32_t channels, int32_t hw, void* stream);
 
