@@ -50,6 +50,9 @@ EXPORTS = [
     "idb_head_pack", "idb_head_workspace_bytes", "idb_head_loss", "idb_head_logits",
     "idb_head_grad_workspace_bytes", "idb_head_loss_grad", "idb_head_sgd_step",
     "idb_tail_workspace_bytes", "idb_tail_forward", "idb_tail_backward", "idb_sgd_clip_step",
+    "idb_blk_conv_workspace_bytes", "idb_blk_conv_forward", "idb_blk_conv_dgrad", "idb_blk_conv_wgrad",
+    "idb_blk_bn_workspace_bytes", "idb_blk_bn_forward", "idb_blk_bn_backward", "idb_blk_affine", "idb_blk_pack_images",
+    "idb_sgd_clip_table_workspace_bytes", "idb_sgd_clip_step_table",
 ]
 
 
@@ -96,6 +99,11 @@ class TailDesc(C.Structure):
                 ("x", C.c_void_p), ("keep", C.c_void_p), ("bn2_weight", C.c_void_p), ("bn2_bias", C.c_void_p), ("bn2_mean", C.c_void_p),
                 ("bn2_var", C.c_void_p), ("fc_weight", C.c_void_p), ("fc_bias", C.c_void_p), ("feat_weight", C.c_void_p),
                 ("feat_bias", C.c_void_p), ("feat_mean", C.c_void_p), ("feat_var", C.c_void_p)]
+
+
+class BlkConvDesc(C.Structure):
+    _fields_ = [("b", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("ksize", C.c_int32),
+                ("stride", C.c_int32), ("x", C.c_void_p), ("affine", C.c_void_p), ("slope", C.c_void_p), ("weight", C.c_void_p)]
 
 
 class IdbError(RuntimeError):
@@ -211,6 +219,17 @@ def load() -> C.CDLL:
         "idb_tail_backward": (C.c_int, [C.POINTER(TailDesc)] + [vp] * 8 + [i32] + [vp] * 7 + [sz, vp]),
         "idb_sgd_clip_step": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)] + [C.c_double] * 4 + [i32, vp, vp, sz,
                                         vp]),
+        "idb_blk_conv_workspace_bytes": (sz, [i32] * 7 + [C.POINTER(i32), C.POINTER(i32)]),
+        "idb_blk_conv_forward": (C.c_int, [C.POINTER(BlkConvDesc), vp, vp]),
+        "idb_blk_conv_dgrad": (C.c_int, [C.POINTER(BlkConvDesc), vp, vp, vp]),
+        "idb_blk_conv_wgrad": (C.c_int, [C.POINTER(BlkConvDesc), vp, vp, vp, sz, vp]),
+        "idb_blk_bn_workspace_bytes": (sz, [i64, i32, C.POINTER(i32)]),
+        "idb_blk_bn_forward": (C.c_int, [vp, i64, i32, i32, C.c_double, C.c_double] + [vp] * 8 + [sz, vp]),
+        "idb_blk_bn_backward": (C.c_int, [vp, vp, i64, i32] + [vp] * 10 + [sz, vp]),
+        "idb_blk_affine": (C.c_int, [vp] * 5 + [i64, i32, vp, vp]),
+        "idb_blk_pack_images": (C.c_int, [vp, i32, i32, i32, vp, vp]),
+        "idb_sgd_clip_table_workspace_bytes": (sz, [i32]),
+        "idb_sgd_clip_step_table": (C.c_int, [i32, vp, vp, vp, vp] + [C.c_double] * 4 + [i32, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

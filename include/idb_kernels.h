@@ -858,6 +858,70 @@ int idb_sgd_clip_step(int32_t count, float* const* weights, const float* const* 
                       double lr, double momentum, double weight_decay, double max_norm, int32_t first_step, double* total_norm, void* ws,
                       size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The backbone's convolutional trunk in training (iresnet.py's stem and IBasicBlock), as the pieces a block is composed of
+ * (faceposegenerator_amd/frtrunk.py composes them), forward and backward, and the joint clipped SGD step over a table of tensors.
+ * idb_tail's conventions: fp32 state, every product on the exact f32-input MFMA, statistics and cross-workgroup reductions in
+ * double in an order the shapes alone decide, no floating-point atomics (bit-identical from run to run), no synchronisation,
+ * every argument validated before any HIP call.
+ *   Layout: activations and their gradients NHWC [b][h][w][c]; conv weights and their gradients [cout][ky][kx][cin].
+ *   Bounds: cin == 4 or cin % 64 == 0, cout % 64 == 0, both <= 2048; 1 <= h, w <= 128; 1 <= b <= 1024; BatchNorm over
+ *   rows = b h w >= 2 in training, ch % 64 == 0; ksize 3 (pad 1) or 1 (pad 0); stride 1 or 2; ho = (h + 2 pad - ksize) / stride + 1.
+ *   idb_blk_bn_forward: BatchNorm2d over [rows][ch].  Training: shifted sums per (row slice, channel) in double (the shift is row 0),
+ *       merged by one wave per channel (lane l adds slices l, l + 64, ... ascending, then an xor butterfly); mean, biased variance,
+ *       invstd = 1 / sqrt(var + eps), running <- (1 - momentum) old + momentum new (the unbiased variance; in double, rounded once).
+ *       Eval: the running statistics, unchanged.  Outputs: stat double [2][ch] (mean, invstd), affine fp32 [2][ch]
+ *       (sc = gamma invstd, sh = beta - mean sc, each rounded once).  flags int32 [2] is only ever raised (the caller zeroes it):
+ *       [0] a statistic is not finite, [1] var + eps == 0.  idb_blk_bn_workspace_bytes(rows, ch, slices): the workspace of
+ *       idb_blk_bn_forward and idb_blk_bn_backward, 0 for refused shapes.
+ *   idb_blk_conv_forward: out[b][oy][ox][co] = sum a[b][oy s + ky - pad][ox s + kx - pad][ci] w[co][ky][kx][ci] as an fma chain over
+ *       k = (ky, kx, ci) ascending, with a = x, or fma(x, sc, sh) with `affine` (cin's pair), then a > 0 ? a : slope a with `slope`,
+ *       formed in the operand load and never written; an out-of-image tap is an exact 0.
+ *   idb_blk_conv_dgrad: g_in[b][y][x][ci] = sum g_out[b][(y + pad - ky) / s][(x + pad - kx) / s][co] w[co][ky][kx][ci] over the taps
+ *       where the division is exact and in range: the gradient with respect to a (not x).  One grid slab per stride-parity class
+ *       of input pixels, each reducing over the taps that reach it only.  cin % 64 == 0.
+ *   idb_blk_conv_wgrad: d_weight[co][ky][kx][ci] = sum over b, oy, ox of g_out a, a recomputed as in the forward; the reduction in
+ *       `wgrad_slices` slices (idb_blk_conv_workspace_bytes reports them, the dgrad's tiles of 128 rows, and the workspace), the
+ *       slices merged in ascending order in double and rounded once.
+ *   idb_blk_bn_backward: for y = fma(c, sc, sh) and p = slope ? prelu(y) : y with g the gradient of p: g_y = y > 0 ? g : slope g
+ *       (y == 0 takes the slope), d_slope = sum g min(y, 0), d_beta = S1 = sum g_y, d_gamma = S2 = sum g_y xhat,
+ *       g_c = gamma invstd (g_y - S1 / rows - xhat S2 / rows) (+ add, a second gradient of c's shape, NULL: none), in double,
+ *       rounded once.  The sums per (row slice, channel) in double, merged as in idb_blk_bn_forward.
+ *   idb_blk_affine: out = prelu(fma(c, sc, sh)) (slope NULL: no PReLU) + identity (NULL: none), or + fma(identity, scd, shd) with
+ *       id_affine: the stem's activation and the block's residual in one elementwise launch.
+ *   idb_blk_pack_images: float NCHW [b][3][h][w] -> NHWC [b][h][w][4], the fourth channel 0.
+ *   idb_sgd_clip_step_table: idb_sgd_clip_step over 1..1024 tensors whose pointer and numel tables (count entries each) lie in
+ *       DEVICE memory; the same arithmetic and summation order, bit-identical to idb_sgd_clip_step for up to 8 tensors.  The tables'
+ *       contents cannot be validated on the host: the caller guarantees 1 <= numel <= 2^32 and distinct buffers.
+ *       ws: idb_sgd_clip_table_workspace_bytes(count), 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct idb_blk_conv_desc {
+    int32_t b, h, w, cin, cout, ksize, stride;
+    const float* x;           /* [b][h][w][cin] */
+    const float* affine;      /* [2][cin] sc, sh applied while loading; NULL: x as it is */
+    const float* slope;       /* [cin] PReLU after the affine; NULL: none */
+    const float* weight;      /* [cout][ksize][ksize][cin] */
+} idb_blk_conv_desc;
+size_t idb_blk_conv_workspace_bytes(int32_t b, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t ksize, int32_t stride,
+                                    int32_t* wgrad_slices, int32_t* dgrad_row_tiles);
+int idb_blk_conv_forward(const idb_blk_conv_desc* d, float* out, void* stream);
+int idb_blk_conv_dgrad(const idb_blk_conv_desc* d, const float* g_out, float* g_in, void* stream);
+int idb_blk_conv_wgrad(const idb_blk_conv_desc* d, const float* g_out, float* d_weight, void* ws, size_t ws_bytes, void* stream);
+size_t idb_blk_bn_workspace_bytes(int64_t rows, int32_t ch, int32_t* slices);
+int idb_blk_bn_forward(const float* x, int64_t rows, int32_t ch, int32_t training, double eps, double momentum, const float* gamma,
+                       const float* beta, float* running_mean, float* running_var, double* stat, float* affine, int32_t* flags, void* ws,
+                       size_t ws_bytes, void* stream);
+int idb_blk_bn_backward(const float* c, const float* g, int64_t rows, int32_t ch, const double* stat, const float* affine, const float* gamma,
+                        const float* slope, const float* add, float* d_gamma, float* d_beta, float* d_slope, float* g_c, void* ws,
+                        size_t ws_bytes, void* stream);
+int idb_blk_affine(const float* c, const float* affine, const float* slope, const float* identity, const float* id_affine, int64_t rows,
+                   int32_t ch, float* out, void* stream);
+int idb_blk_pack_images(const float* images, int32_t b, int32_t h, int32_t w, float* out, void* stream);
+size_t idb_sgd_clip_table_workspace_bytes(int32_t count);
+int idb_sgd_clip_step_table(int32_t count, float* const* weights, const float* const* grads, float* const* momentum_bufs, const int64_t* numel,
+                            double lr, double momentum, double weight_decay, double max_norm, int32_t first_step, double* total_norm,
+                            void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
