@@ -19,7 +19,7 @@ from __future__ import annotations
 
 from collections import OrderedDict
 from functools import partial
-from typing import Dict, List, Tuple
+from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -43,37 +43,42 @@ def _check_arch(arch: str) -> List[int]:
     return ARCHS[arch]
 
 
-def param_shapes(arch: str = "r100") -> "OrderedDict[str, Tuple[int, ...]]":
-    """State-dict layout of ``iresnet{N}`` (key names and shapes of the module; num_batches_tracked is a 0-d buffer)."""
-    layers = _check_arch(arch)
+def _bn_shapes(out, key: str, c: int) -> None:
+    for f in _BN:
+        out[f"{key}.{f}"] = () if f == "num_batches_tracked" else (c,)
+
+
+def trunk_param_shapes(layers: Sequence[int]) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Key names and shapes of the trunk (everything of ``param_shapes`` in front of ``bn2``) for a list of block counts."""
     out: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
-
-    def bn(key, c):
-        for f in _BN:
-            out[f"{key}.{f}"] = () if f == "num_batches_tracked" else (c,)
-
     out["conv1.weight"] = (64, 3, 3, 3)
-    bn("bn1", 64)
+    _bn_shapes(out, "bn1", 64)
     out["prelu.weight"] = (64,)
     cin = 64
     for i, (nb, planes) in enumerate(zip(layers, PLANES)):
         for j in range(nb):
             k = f"layer{i + 1}.{j}"
             c = cin if j == 0 else planes
-            bn(f"{k}.bn1", c)
+            _bn_shapes(out, f"{k}.bn1", c)
             out[f"{k}.conv1.weight"] = (planes, c, 3, 3)
-            bn(f"{k}.bn2", planes)
+            _bn_shapes(out, f"{k}.bn2", planes)
             out[f"{k}.prelu.weight"] = (planes,)
             out[f"{k}.conv2.weight"] = (planes, planes, 3, 3)
-            bn(f"{k}.bn3", planes)
+            _bn_shapes(out, f"{k}.bn3", planes)
             if j == 0:
                 out[f"{k}.downsample.0.weight"] = (planes, c, 1, 1)
-                bn(f"{k}.downsample.1", planes)
+                _bn_shapes(out, f"{k}.downsample.1", planes)
         cin = planes
-    bn("bn2", 512)
+    return out
+
+
+def param_shapes(arch: str = "r100") -> "OrderedDict[str, Tuple[int, ...]]":
+    """State-dict layout of ``iresnet{N}`` (key names and shapes of the module; num_batches_tracked is a 0-d buffer)."""
+    out = trunk_param_shapes(_check_arch(arch))
+    _bn_shapes(out, "bn2", 512)
     out["fc.weight"] = (EMBED, 512 * 49)
     out["fc.bias"] = (EMBED,)
-    bn("features", EMBED)
+    _bn_shapes(out, "features", EMBED)
     return out
 
 

@@ -1,6 +1,5 @@
 // The convolutional trunk of the face-recognition backbone in training (ID-Booth's FR_training/backbones/iresnet.py: the stem and
-// IBasicBlock), forward and backward, as the pieces a block is composed of, and the loop's joint clip_grad_norm_ + SGD step over a
-// table of tensors kept in device memory.  fp32 state, every product on the exact f32-input MFMA (v_mfma_f32_32x32x2_f32), every
+// IBasicBlock), forward and backward, as the pieces a block is composed of.  fp32 state, every product on the exact f32-input MFMA (v_mfma_f32_32x32x2_f32), every
 // statistic and cross-workgroup reduction in double in an order the shapes alone decide, no floating-point atomics, every index in
 // 64 bits, tile rows and columns past the end loaded as zeros and never stored.
 //   Activations and their gradients are NHWC [b][h][w][c]; conv weights and their gradients are [cout][ky][kx][cin].
@@ -17,37 +16,15 @@
 //             apply     g_c = gamma invstd (g_y - S1 / n - xhat S2 / n) (+ a second gradient), rounded once
 //   affine    out = prelu(fma(c, sc, sh)) (+ identity or + fma(cd, scd, shd)): the stem's activation and the block's residual
 //   pack      float NCHW [b][3][h][w] -> NHWC [b][h][w][4], the fourth channel 0
-//   sgd       idb_tail.hip's three kernels with the tensor list read from device memory
-#include "idb_common.h"
+// The tile helpers are idb_f32mma.h's; the loop's clipped SGD step over a table of tensors is idb_sgd.hip.
+#include "idb_f32mma.h"
 #include <math.h>
 
 namespace {
 
-constexpr int TM = 128;            // tile rows
-constexpr int TK = 32;             // reduction steps per LDS stage
-constexpr int LDR = TK + 1;        // stride of an operand staged [row][k]
-constexpr int LDK = TM + 32;       // stride of an operand staged [k][row]
 constexpr int BLK_MAX_B = 1024, BLK_MAX_C = 2048, BLK_MAX_HW = 128;
 constexpr int BLK_FILL = 256;      // workgroups that fill the machine
 constexpr int BLK_MAX_WSLICES = 64, BLK_MAX_SSLICES = 1024;
-constexpr int SGD_PARTS = 1024, SGD_TABLE_MAX = 1024;
-
-__device__ __forceinline__ int tile_row(int t, int reg, int h) { return t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h; }
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// fixed-order block sum of 256 threads (idb_tail.hip): xor butterfly in the wave, then the four wave totals left to right
-__device__ __forceinline__ double block_sum_d(double v, double* lds4) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
-}
 
 // the activation a conv reads: fma(x, sc, sh), one rounding, then PReLU (one more on the negative side)
 __device__ __forceinline__ f32x4 act4(f32x4 x, f32x4 sc, f32x4 sh, f32x4 sl, bool affine, bool prelu) {
@@ -59,47 +36,6 @@ __device__ __forceinline__ f32x4 act4(f32x4 x, f32x4 sc, f32x4 sh, f32x4 sl, boo
         a[e] = v;
     }
     return a;
-}
-
-// One LDS stage of 32 reduction steps on a 128-row tile of 32 WN columns.  WN = 4: wave w owns columns 32 w and all four 32-row
-// subtiles; WN = 2: wave w owns columns 32 (w & 1) and the subtiles 2 (w >> 1), 2 (w >> 1) + 1.
-// AR / BR: the operand is staged [row][k] (stride LDR), else [k][row] (stride LDK).
-template <bool AR, bool BR, int WN>
-__device__ __forceinline__ void mma_stage(const float* sA, const float* sB, f32x16 (&acc)[WN]) {
-    const int l = threadIdx.x & 63, w = threadIdx.x >> 6, r = l & 31, h = l >> 5, wc = w % WN, wr = (w / WN) * WN;
-#pragma unroll
-    for (int kk = 0; kk < TK; kk += 2) {
-        const float bv = BR ? sB[(wc * 32 + r) * LDR + kk + h] : sB[(kk + h) * LDK + wc * 32 + r];
-#pragma unroll
-        for (int t = 0; t < WN; ++t) {
-            const float av = AR ? sA[((wr + t) * 32 + r) * LDR + kk + h] : sA[(kk + h) * LDK + (wr + t) * 32 + r];
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[t], 0, 0, 0);
-        }
-    }
-}
-
-// [row][k] staging: thread t holds columns 4 (t & 7) .. + 3 of rows (t >> 3) + 32 i, i < NI
-template <int NI>
-__device__ __forceinline__ void stash_rows(float* lds, const f32x4 (&v)[4]) {
-    const int c = (threadIdx.x & 7) * 4, r = threadIdx.x >> 3;
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) lds[(r + 32 * i) * LDR + c + e] = v[i][e];
-}
-// [k][row] staging: thread t holds columns 4 (t & 31) .. + 3 of reduction rows (t >> 5) + 8 i
-__device__ __forceinline__ void stash_cols(float* lds, const f32x4 (&v)[4]) {
-    const int c = (threadIdx.x & 31) * 4, r = threadIdx.x >> 5;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) *(f32x4*)(lds + (r + 8 * i) * LDK + c) = v[i];
-}
-
-template <int WN>
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[WN]) {
-#pragma unroll
-    for (int t = 0; t < WN; ++t)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
 }
 
 struct ConvGeo {
@@ -492,68 +428,7 @@ __global__ __launch_bounds__(256) void blk_pack_kernel(const float* __restrict__
     *(f32x4*)(out + i * 4) = v;
 }
 
-// ---- clip_grad_norm_ and SGD over a table of tensors in device memory (idb_tail.hip's arithmetic and order) ----------------------------
-struct SgdTable {
-    float* const* w;
-    const float* const* g;
-    float* const* buf;
-    const long long* n;
-};
-
-__device__ __forceinline__ int sgd_parts(long long n) {
-    const long long want = (n + 4095) / 4096;
-    return want < SGD_PARTS ? (int)want : SGD_PARTS;
-}
-
-__global__ __launch_bounds__(256) void sgd_table_sqsum_kernel(SgdTable L, double* __restrict__ out) {
-    __shared__ double lds4[4];
-    const int ti = blockIdx.y;
-    const long long n = L.n[ti];
-    const int np = sgd_parts(n);
-    if ((int)blockIdx.x >= np) return;
-    const float* g = L.g[ti];
-    double s = 0.0;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += np * 256LL) {
-        const double v = (double)g[i];
-        s += v * v;
-    }
-    s = block_sum_d(s, lds4);
-    if (threadIdx.x == 0) out[(long long)ti * SGD_PARTS + blockIdx.x] = s;
-}
-
-__global__ __launch_bounds__(256) void sgd_table_norm_kernel(SgdTable L, int count, const double* __restrict__ parts, double* __restrict__ total_norm) {
-    __shared__ double lds4[4];
-    double sum = 0.0;
-    for (int ti = 0; ti < count; ++ti) {
-        const int np = sgd_parts(L.n[ti]);
-        double s = 0.0;
-        for (int i = threadIdx.x; i < np; i += 256) s += parts[(long long)ti * SGD_PARTS + i];
-        sum += block_sum_d(s, lds4);
-    }
-    if (threadIdx.x == 0) *total_norm = sqrt(sum);
-}
-
-__global__ __launch_bounds__(256) void sgd_table_step_kernel(SgdTable L, const double* __restrict__ total_norm, double lr, double momentum, double wd,
-                                                             double max_norm, int first) {
-    const int ti = blockIdx.y;
-    const long long n = L.n[ti];
-    const int np = sgd_parts(n);
-    if ((int)blockIdx.x >= np) return;
-    const double q = max_norm / (*total_norm + 1e-6), coef = q < 1.0 ? q : 1.0;
-    float* w = L.w[ti];
-    const float* g = L.g[ti];
-    float* buf = L.buf[ti];
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += np * 256LL) {
-        const double d = coef * (double)g[i] + wd * (double)w[i];
-        const float b = (float)(first ? d : momentum * (double)buf[i] + d);
-        buf[i] = b;
-        w[i] = (float)((double)w[i] - lr * (double)b);
-    }
-}
-
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-inline size_t blk_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 inline bool conv_dims_ok(int b, int h, int w, int cin, int cout, int ks, int stride) {
     return b >= 1 && b <= BLK_MAX_B && h >= 1 && h <= BLK_MAX_HW && w >= 1 && w <= BLK_MAX_HW && (cin == 4 || (cin >= 64 && cin % 64 == 0)) &&
            cin <= BLK_MAX_C && cout >= 64 && cout % 64 == 0 && cout <= BLK_MAX_C && (ks == 1 || ks == 3) && (stride == 1 || stride == 2);
@@ -591,7 +466,7 @@ ConvPlan conv_plan(const ConvGeo& g) {
     if (ks < 1) ks = 1;
     p.per = (steps + ks - 1) / ks;
     p.slices = (steps + p.per - 1) / p.per;
-    p.total = blk_align(sizeof(float) * (size_t)p.slices * g.cout * g.K);
+    p.total = align256(sizeof(float) * (size_t)p.slices * g.cout * g.K);
     return p;
 }
 
@@ -622,8 +497,8 @@ BnPlan bn_plan(long long rows, int ch) {
     p.per = (int)((rows + ss - 1) / ss);
     p.slices = (int)((rows + p.per - 1) / p.per);
     size_t o = 0;
-    p.part = o, o += blk_align(sizeof(double) * 3 * (size_t)p.slices * ch);
-    p.cmean = o, o += blk_align(sizeof(double) * 2 * (size_t)ch);
+    p.part = o, o += align256(sizeof(double) * 3 * (size_t)p.slices * ch);
+    p.cmean = o, o += align256(sizeof(double) * 2 * (size_t)ch);
     p.total = o;
     return p;
 }
@@ -771,35 +646,5 @@ extern "C" int idb_blk_pack_images(const float* images, int32_t b, int32_t h, in
     const long long pixels = (long long)b * h * w;
     hipLaunchKernelGGL(blk_pack_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, (hipStream_t)stream, images, pixels, h * w, out);
     IDB_CHECK_LAUNCH("idb_blk_pack_images");
-    return IDB_OK;
-}
-
-extern "C" size_t idb_sgd_clip_table_workspace_bytes(int32_t count) {
-    if (count < 1 || count > SGD_TABLE_MAX) return 0;
-    return sizeof(double) * (size_t)count * SGD_PARTS;
-}
-
-extern "C" int idb_sgd_clip_step_table(int32_t count, float* const* weights, const float* const* grads, float* const* momentum_bufs,
-                                       const int64_t* numel, double lr, double momentum, double weight_decay, double max_norm,
-                                       int32_t first_step, double* total_norm, void* ws, size_t ws_bytes, void* stream) {
-    IDB_REQUIRE(count >= 1 && count <= SGD_TABLE_MAX, "idb_sgd_clip_step_table: 1..%d tensors", SGD_TABLE_MAX);
-    IDB_REQUIRE(weights && grads && momentum_bufs && numel && total_norm, "idb_sgd_clip_step_table: null pointer");
-    IDB_REQUIRE(((((uintptr_t)total_norm) | ((uintptr_t)weights) | ((uintptr_t)grads) | ((uintptr_t)momentum_bufs) | ((uintptr_t)numel)) & 7) == 0,
-                "idb_sgd_clip_step_table: total_norm and the tables 8-byte aligned");
-    IDB_REQUIRE(lr >= 0.0 && lr <= 1e4 && momentum >= 0.0 && momentum < 1.0 && weight_decay >= 0.0 && weight_decay <= 1e4 && max_norm > 0.0 &&
-                    max_norm <= 1e30,
-                "idb_sgd_clip_step_table: lr in [0, 1e4], momentum in [0, 1), weight_decay in [0, 1e4], max_norm in (0, 1e30]");
-    IDB_REQUIRE(ws && idb_aligned16(ws) && ws_bytes >= sizeof(double) * (size_t)count * SGD_PARTS,
-                "idb_sgd_clip_step_table: workspace too small or unaligned");
-    SgdTable L;
-    L.w = weights, L.g = grads, L.buf = momentum_bufs, L.n = (const long long*)numel;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sgd_table_sqsum_kernel, dim3(SGD_PARTS, count), dim3(256), 0, st, L, (double*)ws);
-    IDB_CHECK_LAUNCH("idb_sgd_clip_step_table(norm partials)");
-    hipLaunchKernelGGL(sgd_table_norm_kernel, dim3(1), dim3(256), 0, st, L, count, (const double*)ws, total_norm);
-    IDB_CHECK_LAUNCH("idb_sgd_clip_step_table(norm)");
-    hipLaunchKernelGGL(sgd_table_step_kernel, dim3(SGD_PARTS, count), dim3(256), 0, st, L, (const double*)total_norm, lr, momentum, weight_decay,
-                       max_norm, first_step != 0);
-    IDB_CHECK_LAUNCH("idb_sgd_clip_step_table");
     return IDB_OK;
 }

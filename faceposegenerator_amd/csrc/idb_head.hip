@@ -16,9 +16,10 @@
 //          in the accumulator registers from the forward's log-sum-exp, and the accumulator tile is the A operand of the second product
 //          as it stands (its column is on the lane, its rows are the reduction index): dX = G Wn per (row tile, class block) with the
 //          blocks merged in ascending order, dW = G^T X per class tile over all row tiles, projected and written as kernel.grad
-//   sgd    clip_grad_norm_ and SGD with momentum on the kernel: squared-sum partials, then the step (idb_head_sgd_step), then pack
+//   sgd    clip_grad_norm_ and SGD with momentum on the kernel (idb_head_sgd_step): squared-sum partials, then the norm and the step in
+//          one launch, both made of idb_sgd.h's device functions (the arithmetic of idb_sgd.hip), then pack
 // No floating-point atomics, every sum in a fixed order that depends on the shapes alone: results are bit-identical from run to run.
-#include "idb_common.h"
+#include "idb_sgd.h"
 #include <math.h>
 
 namespace {
@@ -30,8 +31,6 @@ constexpr int HEAD_MAX_B = 65536, HEAD_MAX_D = 4096, HEAD_MAX_C = 1 << 20;
 constexpr int HEAD_FILL = 256;     // workgroups that fill the machine (CUs)
 constexpr int HEAD_MAX_WGS = 2048; // column blocks x row tiles stays near this: bounds the workspace at the largest shapes
 constexpr double ADA_EPS = 1e-3;
-
-__device__ __forceinline__ int tile_row(int t, int reg, int h) { return t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 // Thread t stages columns 4 (t & 7) .. + 3 of rows (t >> 3) + 32 i, i < T, of an operand: 8 lanes read 128 contiguous bytes of a row.
 template <int T>
@@ -109,21 +108,6 @@ __device__ __forceinline__ void head_tile(const float* a, int na, const float* b
 // torch.clamp keeps a NaN; fminf / fmaxf would not
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 __device__ __forceinline__ double clampd(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// fixed-order block sum of 256 threads: xor butterfly in the wave, then the four wave totals left to right; every thread gets it
-__device__ __forceinline__ double block_sum_d(double v, double* lds4) {
-    v = wave_sum_d(v);
-    __syncthreads();                                   // lds4 may still be read from the previous sum
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
-}
 
 // ---- pack -------------------------------------------------------------------------------------------------------------------------
 // One workgroup per 64 columns (classes).  Pass 1: thread (g = t >> 6, c = t & 63) sums kernel[k][c]^2 over k = g, g + 4, ... in double
@@ -621,43 +605,25 @@ __global__ __launch_bounds__(256) void head_grad_rows_kernel(const float* __rest
     }
 }
 
-// ---- clip_grad_norm_ and SGD ------------------------------------------------------------------------------------------------------
-constexpr int SGD_PARTS = 1024;
-
-// workgroup b sums the squares of elements 256 b + t + 256 gridDim.x i in order, then the fixed block sum
+// ---- clip_grad_norm_ and SGD (idb_sgd.h's arithmetic on one tensor) ------------------------------------------------------------------
+// one workgroup per part
 __global__ __launch_bounds__(256) void head_sqsum_kernel(const float* __restrict__ g, long long n, double* __restrict__ parts) {
     __shared__ double lds4[4];
-    double s = 0.0;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += gridDim.x * 256LL) {
-        const double v = (double)g[i];
-        s += v * v;
-    }
-    s = block_sum_d(s, lds4);
+    const double s = sgd_sqsum_part(g, n, gridDim.x, lds4);
     if (threadIdx.x == 0) parts[blockIdx.x] = s;
 }
 
-// every workgroup adds the partials in the same fixed order; the step itself is evaluated in double per element and each fp32 state
-// (the momentum buffer, the weight) is rounded once
+// every workgroup adds the partials in the same fixed order (no launch of one workgroup between the two), then steps its part
 __global__ __launch_bounds__(256) void head_sgd_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ buf, long long n,
-                                                       const double* __restrict__ parts, int nparts, double lr, double momentum, double wd,
+                                                       const double* __restrict__ parts, double lr, double momentum, double wd,
                                                        double max_norm, int first, double* __restrict__ total_norm) {
     __shared__ double lds4[4];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 256) s += parts[i];
-    const double norm = sqrt(block_sum_d(s, lds4));
-    const double q = max_norm / (norm + 1e-6), coef = q < 1.0 ? q : 1.0;
+    const double norm = sqrt(sgd_sum_parts(parts, gridDim.x, lds4));
     if (blockIdx.x == 0 && threadIdx.x == 0) *total_norm = norm;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += gridDim.x * 256LL) {
-        const double d = coef * (double)g[i] + wd * (double)w[i];
-        const float b = (float)(first ? d : momentum * (double)buf[i] + d);
-        buf[i] = b;
-        w[i] = (float)((double)w[i] - lr * (double)b);
-    }
+    sgd_step_part(w, g, buf, n, gridDim.x, sgd_clip_coef(max_norm, norm), lr, momentum, wd, first);
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-inline size_t head_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct HeadPlan {
     int ta, row_tiles, tiles, per, col_blocks;
     size_t en, zt, m, s, a, total;                     // workspace offsets
@@ -679,11 +645,11 @@ HeadPlan head_plan(int b, int d, int c) {
     p.per = (p.tiles + cap - 1) / cap;
     p.col_blocks = (p.tiles + p.per - 1) / p.per;
     size_t o = 0;
-    p.en = o, o += head_align(sizeof(float) * (size_t)b * d);
-    p.zt = o, o += head_align(sizeof(float) * (size_t)b);
-    p.m = o, o += head_align(sizeof(float) * (size_t)p.col_blocks * b);
-    p.s = o, o += head_align(sizeof(double) * (size_t)p.col_blocks * b);
-    p.a = o, o += head_align(sizeof(int32_t) * (size_t)p.col_blocks * b);
+    p.en = o, o += align256(sizeof(float) * (size_t)b * d);
+    p.zt = o, o += align256(sizeof(float) * (size_t)b);
+    p.m = o, o += align256(sizeof(float) * (size_t)p.col_blocks * b);
+    p.s = o, o += align256(sizeof(double) * (size_t)p.col_blocks * b);
+    p.a = o, o += align256(sizeof(int32_t) * (size_t)p.col_blocks * b);
     p.total = o;
     return p;
 }
@@ -765,8 +731,8 @@ HeadGradPlan head_grad_plan(int b, int d, int c) {
     g.chunks = (d + 32 * GK - 1) / (32 * GK);
     g.ok = (long long)g.blocks * b * d <= GRAD_MAX_PART;
     size_t o = head_plan(b, d, c).total;
-    g.part = o, o += head_align(sizeof(float) * (size_t)g.blocks * b * d);
-    g.dot = o, o += head_align(sizeof(double) * (size_t)g.blocks * b);
+    g.part = o, o += align256(sizeof(float) * (size_t)g.blocks * b * d);
+    g.dot = o, o += align256(sizeof(double) * (size_t)g.blocks * b);
     g.total = o;
     return g;
 }
@@ -888,12 +854,11 @@ extern "C" int idb_head_sgd_step(float* kernel, const float* grad, float* moment
                 IDB_HEAD_SGD_WS_BYTES);
     hipStream_t st = (hipStream_t)stream;
     const long long n = (long long)d * c;
-    const long long want = (n + 4095) / 4096;
-    const int nparts = want < SGD_PARTS ? (int)want : SGD_PARTS;
+    const int nparts = sgd_parts(n);
     hipLaunchKernelGGL(head_sqsum_kernel, dim3(nparts), dim3(256), 0, st, grad, n, (double*)ws);
     IDB_CHECK_LAUNCH("idb_head_sgd_step(norm)");
-    hipLaunchKernelGGL(head_sgd_kernel, dim3(nparts), dim3(256), 0, st, kernel, grad, momentum_buf, n, (const double*)ws, nparts, lr, momentum,
-                       weight_decay, max_norm, first_step != 0, total_norm);
+    hipLaunchKernelGGL(head_sgd_kernel, dim3(nparts), dim3(256), 0, st, kernel, grad, momentum_buf, n, (const double*)ws, lr, momentum, weight_decay,
+                       max_norm, first_step != 0, total_norm);
     IDB_CHECK_LAUNCH("idb_head_sgd_step");
     return idb_head_pack(kernel, d, c, wn, col_norm, bad_cols, stream);
 }

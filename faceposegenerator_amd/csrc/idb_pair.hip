@@ -9,7 +9,7 @@
 // owns 32 columns (rows of B) and all 128 rows of the tile, so every lane owns ONE row of B: whatever is reduced per row of B (k
 // nearest candidates of a query, the nearest neighbour, counts) stays in that lane's registers, and the two half-waves that share a
 // column are merged afterwards.  Everything is deterministic: integer atomics only, float sums in a fixed order.
-#include "idb_common.h"
+#include "idb_f32mma.h"
 
 namespace {
 
@@ -26,7 +26,6 @@ struct Operand {
     int n;
 };
 
-__device__ __forceinline__ int tile_row(int t, int reg, int h) { return t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 __device__ __forceinline__ float dist2_of(float na, float nb, float dot) {
     const float d = (na + nb) - 2.f * dot;
     return d > 0.f ? d : 0.f;      // never -0: the bits of a distance order as unsigned integers
@@ -356,20 +355,19 @@ __global__ __launch_bounds__(64) void pair_poly_reduce_kernel(const float* __res
 constexpr int PAIR_MAX_N = 1 << 22, PAIR_MAX_D = 1 << 16;
 inline int pair_blocks(int n) { return (n + PT - 1) / PT; }
 inline int pair_splits(int rows) { return pair_blocks(rows) < PAIR_MAX_SPLITS ? pair_blocks(rows) : PAIR_MAX_SPLITS; }
-inline size_t pair_align(size_t b) { return (b + 255) & ~(size_t)255; }
 inline bool pair_vec(int d, const void* a, const void* b, const void* s) {
     return d % 4 == 0 && idb_aligned16(a) && idb_aligned16(b) && (!s || idb_aligned16(s));
 }
 inline bool pair_dims_ok(int na, int nb, int d) { return na > 0 && nb > 0 && d > 0 && na <= PAIR_MAX_N && nb <= PAIR_MAX_N && d <= PAIR_MAX_D; }
 
 size_t pair_ws_bytes(int mode, int na, int nb, int subsets) {
-    const size_t norms = pair_align(sizeof(float) * na) + pair_align(sizeof(float) * nb);
+    const size_t norms = align256(sizeof(float) * na) + align256(sizeof(float) * nb);
     switch (mode) {
         case IDB_PAIR_DIST2:
         case IDB_PAIR_PRDC: return norms;
-        case IDB_PAIR_KNN: return pair_align(sizeof(float) * na) + pair_align(sizeof(float) * 2 * pair_splits(na) * (size_t)na * KNN_MAX);
-        case IDB_PAIR_NEAREST: return norms + 2 * pair_align(sizeof(float) * 2 * pair_splits(na) * (size_t)nb);
-        case IDB_PAIR_POLY: return pair_align(sizeof(float) * 3 * (size_t)subsets * pair_blocks(na) * pair_blocks(na));
+        case IDB_PAIR_KNN: return align256(sizeof(float) * na) + align256(sizeof(float) * 2 * pair_splits(na) * (size_t)na * KNN_MAX);
+        case IDB_PAIR_NEAREST: return norms + 2 * align256(sizeof(float) * 2 * pair_splits(na) * (size_t)nb);
+        case IDB_PAIR_POLY: return align256(sizeof(float) * 3 * (size_t)subsets * pair_blocks(na) * pair_blocks(na));
     }
     return 0;
 }
@@ -396,7 +394,7 @@ extern "C" int idb_pair_dist2(const float* a, int32_t na, const float* b, int32_
     IDB_REQUIRE(ws_bytes >= pair_ws_bytes(IDB_PAIR_DIST2, na, nb, 0) && idb_aligned16(ws), "idb_pair_dist2: workspace too small or unaligned");
     hipStream_t st = (hipStream_t)stream;
     float* nra = (float*)ws;
-    float* nrb = (float*)((char*)ws + pair_align(sizeof(float) * na));
+    float* nrb = (float*)((char*)ws + align256(sizeof(float) * na));
     int rc = pair_norms("idb_pair_dist2", a, shift, na, d, nra, st);
     if (rc == IDB_OK) rc = pair_norms("idb_pair_dist2", b, shift, nb, d, nrb, st);
     if (rc != IDB_OK) return rc;
@@ -414,7 +412,7 @@ extern "C" int idb_pair_knn_radii(const float* x, int32_t n, int32_t d, const fl
     IDB_REQUIRE(ws_bytes >= pair_ws_bytes(IDB_PAIR_KNN, n, n, 0) && idb_aligned16(ws), "idb_pair_knn_radii: workspace too small or unaligned");
     hipStream_t st = (hipStream_t)stream;
     float* nx = (float*)ws;
-    float* lists = (float*)((char*)ws + pair_align(sizeof(float) * n));
+    float* lists = (float*)((char*)ws + align256(sizeof(float) * n));
     const int splits = pair_splits(n);
     int rc = pair_norms("idb_pair_knn_radii", x, shift, n, d, nx, st);
     if (rc != IDB_OK) return rc;
@@ -434,7 +432,7 @@ extern "C" int idb_pair_prdc_counts(const float* real, int32_t nr, const float* 
     IDB_REQUIRE(ws_bytes >= pair_ws_bytes(IDB_PAIR_PRDC, nr, ng, 0) && idb_aligned16(ws), "idb_pair_prdc_counts: workspace too small or unaligned");
     hipStream_t st = (hipStream_t)stream;
     float* nra = (float*)ws;
-    float* nrb = (float*)((char*)ws + pair_align(sizeof(float) * nr));
+    float* nrb = (float*)((char*)ws + align256(sizeof(float) * nr));
     int rc = pair_norms("idb_pair_prdc_counts", real, shift, nr, d, nra, st);
     if (rc == IDB_OK) rc = pair_norms("idb_pair_prdc_counts", gen, shift, ng, d, nrb, st);
     if (rc != IDB_OK) return rc;
@@ -456,12 +454,12 @@ extern "C" int idb_pair_nearest(const float* a, int32_t na, const float* b, int3
     IDB_REQUIRE(ws_bytes >= pair_ws_bytes(IDB_PAIR_NEAREST, na, nb, 0) && idb_aligned16(ws), "idb_pair_nearest: workspace too small or unaligned");
     hipStream_t st = (hipStream_t)stream;
     const int splits = pair_splits(na);
-    const size_t part = pair_align(sizeof(float) * 2 * splits * (size_t)nb);
+    const size_t part = align256(sizeof(float) * 2 * splits * (size_t)nb);
     char* p = (char*)ws;
     float* nra = (float*)p;
-    p += pair_align(sizeof(float) * na);
+    p += align256(sizeof(float) * na);
     float* nrb = (float*)p;
-    p += pair_align(sizeof(float) * nb);
+    p += align256(sizeof(float) * nb);
     float* ws_min = (float*)p;
     int32_t* ws_idx = (int32_t*)(p + part);
     int rc = pair_norms("idb_pair_nearest", a, shift, na, d, nra, st);

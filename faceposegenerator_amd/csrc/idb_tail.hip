@@ -1,6 +1,5 @@
 // The embedding stage of the face-recognition backbone in training (ID-Booth's FR_training/backbones/iresnet.py: bn2 -> flatten ->
-// dropout -> fc -> features, then the loop's F.normalize), forward and backward, and the loop's joint clip_grad_norm_ + SGD step over a
-// list of tensors.  fp32 state, the three [b] x [hw ch] x [n] products on the exact f32-input MFMA (v_mfma_f32_32x32x2_f32), every
+// dropout -> fc -> features, then the loop's F.normalize), forward and backward.  fp32 state, the three [b] x [hw ch] x [n] products on the exact f32-input MFMA (v_mfma_f32_32x32x2_f32), every
 // statistic and reduction in double in an order the shapes alone decide, no floating-point atomics.
 //   x is NHWC [b][hw][ch]; with k = p ch + c the flattened row of sample i is x[i K + k], K = hw ch: the device order of fc.weight's
 //   columns, of the keep-mask and of every [b][K] array here.
@@ -17,37 +16,15 @@
 //             bn2       those partials in ascending order: d bn2.weight, d bn2.bias, the two means
 //             dx        gamma invstd (g_y - mean - xhat mean(g_y xhat)), optional
 //             wgrad     dW = g_z^T d with d recomputed in the load path, all of the batch inside one workgroup
-//   sgd       squared-sum partials per tensor, their fixed-order total, the step
-#include "idb_common.h"
+// The tile helpers are idb_f32mma.h's, instantiated at 4 column groups; the loop's clipped SGD step is idb_sgd.hip.
+#include "idb_f32mma.h"
 #include <math.h>
 
 namespace {
 
-constexpr int TM = 128;            // tile rows and columns (4 waves x 32 columns, 4 x 32 rows per wave)
-constexpr int TK = 32;             // reduction steps per LDS stage
-constexpr int LDR = TK + 1;        // stride of an operand staged [row][k] (idb_head.hip)
-constexpr int LDK = TM + 32;       // stride of an operand staged [k][row]: the two half-waves of a read hit disjoint banks
 constexpr int TAIL_MAX_B = 1024, TAIL_MAX_CH = 2048, TAIL_MAX_HW = 64, TAIL_MAX_N = 1024;
 constexpr int TAIL_FILL = 256;     // workgroups that fill the machine
 constexpr int TAIL_MAX_SLICES = 64;
-constexpr int SGD_MAX_TENSORS = 8, SGD_PARTS = 1024;
-
-__device__ __forceinline__ int tile_row(int t, int reg, int h) { return t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h; }
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// fixed-order block sum of 256 threads: xor butterfly in the wave, then the four wave totals left to right; every thread gets it
-__device__ __forceinline__ double block_sum_d(double v, double* lds4) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
-}
 
 template <typename T> __device__ __forceinline__ f32x4 load4(const T* p);
 template <> __device__ __forceinline__ f32x4 load4<float>(const float* p) { return *(const f32x4*)p; }
@@ -69,43 +46,6 @@ __device__ __forceinline__ f32x4 dropped4(f32x4 x, f32x4 sc, f32x4 sh, uint32_t 
         d[e] = ((keep4 >> (8 * e)) & 0xffu) ? a * inv_keep : 0.f;
     }
     return d;
-}
-
-// one LDS stage of 32 reduction steps.  AR / BR: the operand is staged [row][k] (stride LDR), else [k][row] (stride LDK).
-template <bool AR, bool BR>
-__device__ __forceinline__ void mma_stage(const float* sA, const float* sB, f32x16 (&acc)[4]) {
-    const int l = threadIdx.x & 63, w = threadIdx.x >> 6, r = l & 31, h = l >> 5;
-#pragma unroll
-    for (int kk = 0; kk < TK; kk += 2) {               // A[i = l & 31][k = l >> 5], B[k = l >> 5][j = l & 31]
-        const float bv = BR ? sB[(w * 32 + r) * LDR + kk + h] : sB[(kk + h) * LDK + w * 32 + r];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float av = AR ? sA[(t * 32 + r) * LDR + kk + h] : sA[(kk + h) * LDK + t * 32 + r];
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[t], 0, 0, 0);
-        }
-    }
-}
-
-// [row][k] staging: thread t holds columns 4 (t & 7) .. + 3 of rows (t >> 3) + 32 i
-__device__ __forceinline__ void stash_rows(float* lds, const f32x4 (&v)[4]) {
-    const int c = (threadIdx.x & 7) * 4, r = threadIdx.x >> 3;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) lds[(r + 32 * i) * LDR + c + e] = v[i][e];
-}
-// [k][row] staging: thread t holds columns 4 (t & 31) .. + 3 of reduction rows (t >> 5) + 8 i
-__device__ __forceinline__ void stash_cols(float* lds, const f32x4 (&v)[4]) {
-    const int c = (threadIdx.x & 31) * 4, r = threadIdx.x >> 5;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) *(f32x4*)(lds + (r + 8 * i) * LDK + c) = v[i];
-}
-
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[4]) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
 }
 
 // ---- forward: bn2 statistics ------------------------------------------------------------------------------------------------------
@@ -179,7 +119,7 @@ __global__ __launch_bounds__(256) void tail_fc_kernel(const T* __restrict__ x, c
     const int steps = K / TK, s0 = blockIdx.z * per, s1 = min(steps, s0 + per);
     const int kc = (threadIdx.x & 7) * 4, rr = threadIdx.x >> 3;
     f32x16 acc[4];
-    zero_acc(acc);
+    zero_acc<4>(acc);
     f32x4 va[4], vb[4];
     auto fetch = [&](int k0) {
         const int k = k0 + kc, c = k % ch;
@@ -199,11 +139,11 @@ __global__ __launch_bounds__(256) void tail_fc_kernel(const T* __restrict__ x, c
     fetch(s0 * TK);
     for (int s = s0; s < s1; ++s) {
         __syncthreads();
-        stash_rows(sA, va);
-        stash_rows(sB, vb);
+        stash_rows<4>(sA, va);
+        stash_rows<4>(sB, vb);
         __syncthreads();
         if (s + 1 < s1) fetch((s + 1) * TK);
-        mma_stage<true, true>(sA, sB, acc);
+        mma_stage<true, true, 4>(sA, sB, acc);
     }
     const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, r = l & 31, h = l >> 5, col = n0 + wv * 32 + r;
     if (col < N) {
@@ -372,7 +312,7 @@ __global__ __launch_bounds__(256) void tail_dgrad_kernel(const float* __restrict
     const int n0 = blockIdx.x * TM, m0 = blockIdx.y * TM;
     const int kc = (threadIdx.x & 7) * 4, rr = threadIdx.x >> 3, cc = (threadIdx.x & 31) * 4, cr = threadIdx.x >> 5;
     f32x16 acc[4];
-    zero_acc(acc);
+    zero_acc<4>(acc);
     f32x4 va[4], vb[4];
     auto fetch = [&](int j0) {
 #pragma unroll
@@ -387,11 +327,11 @@ __global__ __launch_bounds__(256) void tail_dgrad_kernel(const float* __restrict
     fetch(0);
     for (int j0 = 0; j0 < N; j0 += TK) {
         __syncthreads();
-        stash_rows(sA, va);
+        stash_rows<4>(sA, va);
         stash_cols(sB, vb);
         __syncthreads();
         if (j0 + TK < N) fetch(j0 + TK);
-        mma_stage<true, false>(sA, sB, acc);
+        mma_stage<true, false, 4>(sA, sB, acc);
     }
     const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, r = l & 31, h = l >> 5, col = n0 + wv * 32 + r;
     const bool valid = col < K;
@@ -463,7 +403,7 @@ __global__ __launch_bounds__(256) void tail_wgrad_kernel(const float* __restrict
     const int c = kin ? (k0 + cc) % ch : 0;
     const f32x4 sc = *(const f32x4*)(affine + c), sh = *(const f32x4*)(affine + ch + c);
     f32x16 acc[4];
-    zero_acc(acc);
+    zero_acc<4>(acc);
     f32x4 va[4], vb[4];
     auto fetch = [&](int i0) {
 #pragma unroll
@@ -487,7 +427,7 @@ __global__ __launch_bounds__(256) void tail_wgrad_kernel(const float* __restrict
         stash_cols(sB, vb);
         __syncthreads();
         if (i0 + TK < B) fetch(i0 + TK);
-        mma_stage<false, false>(sA, sB, acc);
+        mma_stage<false, false, 4>(sA, sB, acc);
     }
     const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, r = l & 31, h = l >> 5, col = k0 + wv * 32 + r;
     if (col < K) {
@@ -501,64 +441,7 @@ __global__ __launch_bounds__(256) void tail_wgrad_kernel(const float* __restrict
     }
 }
 
-// ---- clip_grad_norm_ and SGD over a list of tensors -------------------------------------------------------------------------------
-struct SgdList {
-    float* w[SGD_MAX_TENSORS];
-    const float* g[SGD_MAX_TENSORS];
-    float* buf[SGD_MAX_TENSORS];
-    long long n[SGD_MAX_TENSORS];
-    int parts[SGD_MAX_TENSORS];
-    int count;
-};
-
-// grid (SGD_PARTS, tensors): workgroup b of a tensor sums the squares of elements 256 b + t + 256 parts i in order.  out: [tensor][SGD_PARTS]
-__global__ __launch_bounds__(256) void sgd_sqsum_kernel(SgdList L, double* __restrict__ out) {
-    __shared__ double lds4[4];
-    const int ti = blockIdx.y, np = L.parts[ti];
-    if ((int)blockIdx.x >= np) return;
-    const float* g = L.g[ti];
-    const long long n = L.n[ti];
-    double s = 0.0;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += np * 256LL) {
-        const double v = (double)g[i];
-        s += v * v;
-    }
-    s = block_sum_d(s, lds4);
-    if (threadIdx.x == 0) out[ti * SGD_PARTS + blockIdx.x] = s;
-}
-
-// one workgroup: tensor after tensor, each tensor's partials strided over the threads and met in the fixed block sum
-__global__ __launch_bounds__(256) void sgd_norm_kernel(SgdList L, const double* __restrict__ parts, double* __restrict__ total_norm) {
-    __shared__ double lds4[4];
-    double sum = 0.0;
-    for (int ti = 0; ti < L.count; ++ti) {
-        double s = 0.0;
-        for (int i = threadIdx.x; i < L.parts[ti]; i += 256) s += parts[ti * SGD_PARTS + i];
-        sum += block_sum_d(s, lds4);
-    }
-    if (threadIdx.x == 0) *total_norm = sqrt(sum);
-}
-
-__global__ __launch_bounds__(256) void sgd_step_kernel(SgdList L, const double* __restrict__ total_norm, double lr, double momentum, double wd,
-                                                       double max_norm, int first) {
-    const int ti = blockIdx.y, np = L.parts[ti];
-    if ((int)blockIdx.x >= np) return;
-    const double q = max_norm / (*total_norm + 1e-6), coef = q < 1.0 ? q : 1.0;
-    float* w = L.w[ti];
-    const float* g = L.g[ti];
-    float* buf = L.buf[ti];
-    const long long n = L.n[ti];
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += np * 256LL) {
-        const double d = coef * (double)g[i] + wd * (double)w[i];
-        const float b = (float)(first ? d : momentum * (double)buf[i] + d);
-        buf[i] = b;
-        w[i] = (float)((double)w[i] - lr * (double)b);
-    }
-}
-
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-inline size_t tail_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct TailPlan {
     int row_tiles, col_tiles, steps, per, k_slices, stat_per, stat_slices;
     size_t spart, fpart, gf, gz, gy, cpart, cmean, total;      // workspace offsets
@@ -589,13 +472,13 @@ TailPlan tail_plan(int b, int ch, int hw, int n) {
     p.stat_per = (rows + ss - 1) / ss;
     p.stat_slices = (rows + p.stat_per - 1) / p.stat_per;
     size_t o = 0;
-    p.spart = o, o += tail_align(sizeof(double) * 2 * (size_t)p.stat_slices * ch);
-    p.fpart = o, o += tail_align(sizeof(float) * (size_t)p.k_slices * b * n);
-    p.gf = o, o += tail_align(sizeof(double) * (size_t)b * n);
-    p.gz = o, o += tail_align(sizeof(float) * (size_t)b * n);
-    p.gy = o, o += tail_align(sizeof(float) * (size_t)b * K);
-    p.cpart = o, o += tail_align(sizeof(double) * 2 * (size_t)p.row_tiles * K);
-    p.cmean = o, o += tail_align(sizeof(double) * 2 * (size_t)ch);
+    p.spart = o, o += align256(sizeof(double) * 2 * (size_t)p.stat_slices * ch);
+    p.fpart = o, o += align256(sizeof(float) * (size_t)p.k_slices * b * n);
+    p.gf = o, o += align256(sizeof(double) * (size_t)b * n);
+    p.gz = o, o += align256(sizeof(float) * (size_t)b * n);
+    p.gy = o, o += align256(sizeof(float) * (size_t)b * K);
+    p.cpart = o, o += align256(sizeof(double) * 2 * (size_t)p.row_tiles * K);
+    p.cmean = o, o += align256(sizeof(double) * 2 * (size_t)ch);
     p.total = o;
     return p;
 }
@@ -733,41 +616,4 @@ extern "C" int idb_tail_backward(const idb_tail_desc* d, const float* g_emb, con
     if (d->x_dtype == IDB_F16) return TAIL_BWD(_Float16);
     return TAIL_BWD(__bf16);
 #undef TAIL_BWD
-}
-
-extern "C" int idb_sgd_clip_step(int32_t count, float* const* weights, const float* const* grads, float* const* momentum_bufs,
-                                 const int64_t* numel, double lr, double momentum, double weight_decay, double max_norm, int32_t first_step,
-                                 double* total_norm, void* ws, size_t ws_bytes, void* stream) {
-    IDB_REQUIRE(count >= 1 && count <= SGD_MAX_TENSORS, "idb_sgd_clip_step: 1..%d tensors", SGD_MAX_TENSORS);
-    IDB_REQUIRE(weights && grads && momentum_bufs && numel && total_norm, "idb_sgd_clip_step: null pointer");
-    IDB_REQUIRE((((uintptr_t)total_norm) & 7) == 0, "idb_sgd_clip_step: total_norm 8-byte aligned");
-    IDB_REQUIRE(lr >= 0.0 && lr <= 1e4 && momentum >= 0.0 && momentum < 1.0 && weight_decay >= 0.0 && weight_decay <= 1e4 && max_norm > 0.0 &&
-                    max_norm <= 1e30,
-                "idb_sgd_clip_step: lr in [0, 1e4], momentum in [0, 1), weight_decay in [0, 1e4], max_norm in (0, 1e30]");
-    IDB_REQUIRE(ws && idb_aligned16(ws) && ws_bytes >= IDB_SGD_CLIP_WS_BYTES, "idb_sgd_clip_step: workspace too small or unaligned (%d bytes)",
-                IDB_SGD_CLIP_WS_BYTES);
-    SgdList L;
-    memset(&L, 0, sizeof(L));
-    L.count = count;
-    for (int i = 0; i < count; ++i) {
-        IDB_REQUIRE(weights[i] && grads[i] && momentum_bufs[i], "idb_sgd_clip_step: tensor %d: null pointer", i);
-        IDB_REQUIRE(numel[i] >= 1 && numel[i] <= (1ll << 32), "idb_sgd_clip_step: tensor %d: 1..2^32 elements", i);
-        L.w[i] = weights[i], L.g[i] = grads[i], L.buf[i] = momentum_bufs[i], L.n[i] = numel[i];
-        for (int j = 0; j < i; ++j)
-            IDB_REQUIRE(weights[i] != weights[j] && momentum_bufs[i] != momentum_bufs[j] && weights[i] != momentum_bufs[j] &&
-                            momentum_bufs[i] != weights[j],
-                        "idb_sgd_clip_step: tensors %d and %d share a weight or momentum buffer", j, i);
-        IDB_REQUIRE(weights[i] != momentum_bufs[i], "idb_sgd_clip_step: tensor %d: weight and momentum buffer are the same", i);
-        const long long want = (numel[i] + 4095) / 4096;
-        L.parts[i] = want < SGD_PARTS ? (int)want : SGD_PARTS;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sgd_sqsum_kernel, dim3(SGD_PARTS, count), dim3(256), 0, st, L, (double*)ws);
-    IDB_CHECK_LAUNCH("idb_sgd_clip_step(norm partials)");
-    hipLaunchKernelGGL(sgd_norm_kernel, dim3(1), dim3(256), 0, st, L, (const double*)ws, total_norm);
-    IDB_CHECK_LAUNCH("idb_sgd_clip_step(norm)");
-    hipLaunchKernelGGL(sgd_step_kernel, dim3(SGD_PARTS, count), dim3(256), 0, st, L, (const double*)total_norm, lr, momentum, weight_decay,
-                       max_norm, first_step != 0);
-    IDB_CHECK_LAUNCH("idb_sgd_clip_step");
-    return IDB_OK;
 }

@@ -43,6 +43,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._frtrain import ClippedSGD, hip_device
 
 LOSSES = {"CosFace": _lib.IDB_HEAD_COSFACE, "ArcFace": _lib.IDB_HEAD_ARCFACE, "AdaFace": _lib.IDB_HEAD_ADAFACE}
 DEFAULT_M = {"CosFace": 0.35, "ArcFace": 0.50, "AdaFace": 0.4}
@@ -209,9 +210,7 @@ class MarginHeader:
         self._state.copy_(torch.tensor([float(batch_mean), float(batch_std)], dtype=torch.float64))
 
     def to(self, device) -> "MarginHeader":
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("MarginHeader runs on a HIP device only (there is no CPU fallback)")
+        dev = hip_device(device, "MarginHeader")
         lib = _lib.load()
         self.device = dev
         self._kernel_dev = self.kernel.to(dev)
@@ -341,39 +340,33 @@ class MarginHeader:
         return out, HeadGrad(d_emb, d_kernel, grad_rows[0])
 
 
-class HeaderSGD:
+class HeaderSGD(ClippedSGD):
     """The header's optimiser of train_FR.py: clip_grad_norm_(header.parameters(), max_norm) (:293), then torch.optim.SGD(lr, momentum,
     weight_decay).step() (:203-208, :296) on header.kernel, fp32 state as torch, one call (idb_head_sgd_step); the header is repacked
-    inside it, so the next forward sees the stepped kernel.  `lr` may be reassigned between steps (the loop's scheduler)."""
+    inside it, so the next forward sees the stepped kernel.  `lr` may be reassigned between steps (the loop's scheduler).  State dict:
+    {"lr", "momentum", "weight_decay", "max_norm", "steps", "momentum_buffer" (fp32 [D, C] on the host, None before a step)}."""
+    _KEY = "momentum_buffer"
+    _EXIST = "a momentum buffer exists"
 
     def __init__(self, header: MarginHeader, lr: float, momentum: float = 0.9, weight_decay: float = 5e-4, max_norm: float = 5.0):
         if not isinstance(header, MarginHeader):
             raise TypeError("HeaderSGD: header must be a MarginHeader")
-        self.lr, self.momentum, self.weight_decay, self.max_norm = float(lr), float(momentum), float(weight_decay), float(max_norm)
-        if not (0.0 <= self.lr <= 1e4 and 0.0 <= self.momentum < 1.0 and 0.0 <= self.weight_decay <= 1e4 and 0.0 < self.max_norm <= 1e30):
-            raise ValueError("HeaderSGD: lr in [0, 1e4], momentum in [0, 1), weight_decay in [0, 1e4], max_norm in (0, 1e30]")
+        super().__init__(lr, momentum, weight_decay, max_norm)
         self.header = header
-        self.steps = 0
-        self._buf: Optional[torch.Tensor] = None
 
-    def state_dict(self) -> Dict[str, object]:
-        """{"lr", "momentum", "weight_decay", "max_norm", "steps", "momentum_buffer" (fp32 [D, C] on the host, None before a step)}."""
-        return {"lr": self.lr, "momentum": self.momentum, "weight_decay": self.weight_decay, "max_norm": self.max_norm,
-                "steps": self.steps, "momentum_buffer": None if self._buf is None else self._buf.detach().cpu().clone()}
+    def _shape(self):
+        return (self.header.in_features, self.header.out_features)
 
-    def load_state_dict(self, sd) -> None:
-        missing = [k for k in ("lr", "momentum", "weight_decay", "max_norm", "steps", "momentum_buffer") if k not in sd]
-        if missing:
-            raise ValueError(f"HeaderSGD state dict without {missing}")
-        buf, steps = sd["momentum_buffer"], int(sd["steps"])
-        shape = (self.header.in_features, self.header.out_features)
-        if (buf is None) != (steps == 0):
-            raise ValueError("HeaderSGD state dict: a momentum buffer exists exactly after the first step")
-        if buf is not None and (not torch.is_tensor(buf) or tuple(buf.shape) != shape):
-            raise ValueError(f"HeaderSGD state dict: momentum_buffer expected {shape}")
-        self.lr, self.momentum, self.weight_decay, self.max_norm = (float(sd[k]) for k in ("lr", "momentum", "weight_decay", "max_norm"))
-        self.steps = steps
-        self._buf = None if buf is None else buf.detach().to(torch.float32).contiguous().clone()
+    def _new_buffers(self) -> torch.Tensor:
+        return torch.empty(self._shape(), dtype=torch.float32, device=self.header.device)
+
+    def _buffers_out(self, buf: torch.Tensor) -> torch.Tensor:
+        return buf.clone()
+
+    def _buffers_in(self, buf) -> torch.Tensor:
+        if not torch.is_tensor(buf) or tuple(buf.shape) != self._shape():
+            raise ValueError(f"HeaderSGD state dict: momentum_buffer expected {self._shape()}")
+        return buf.detach().to(torch.float32).contiguous().clone()
 
     def step(self, grad_kernel: torch.Tensor) -> float:
         """One clipped SGD step on header.kernel with `grad_kernel` (fp32 [D, C], HeadGrad.kernel).  Returns the gradient's L2 norm
@@ -381,16 +374,12 @@ class HeaderSGD:
         hd = self.header
         if hd.device is None:
             raise _lib.IdbError("HeaderSGD.step: the header is not on a device: call .to('cuda:0') first (there is no CPU fallback)")
-        shape = (hd.in_features, hd.out_features)
+        shape = self._shape()
         if not torch.is_tensor(grad_kernel) or tuple(grad_kernel.shape) != shape or grad_kernel.dtype != torch.float32:
             raise ValueError(f"HeaderSGD.step: grad_kernel expected fp32 {shape}")
         dev = hd.device
         g = grad_kernel.to(dev).contiguous()
-        first = self._buf is None
-        if first:
-            self._buf = torch.empty(shape, dtype=torch.float32, device=dev)
-        elif self._buf.device != dev:
-            self._buf = self._buf.to(dev)
+        first = self._begin(dev)
         ws = torch.empty(_lib.IDB_HEAD_SGD_WS_BYTES, dtype=torch.uint8, device=dev)
         both = torch.zeros(16, dtype=torch.uint8, device=dev)      # bytes 0-7 the norm (double), 8-11 the bad columns (int32): one read
         lib = _lib.load()

@@ -27,14 +27,14 @@ fallback), a trunk in training mode, and ``auto_schedule``'s ``ReduceLROnPlateau
 from __future__ import annotations
 
 import ctypes as C
-import math
-from typing import Dict, NamedTuple, Optional, Sequence
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from .frhead import HeaderSGD, MarginHeader
+from ._frtrain import ClippedSGD, hip_device
+from .frhead import HeadGrad, HeadLoss, HeaderSGD, MarginHeader
 
 STAGE_KEYS = ("bn2.weight", "bn2.bias", "bn2.running_mean", "bn2.running_var", "bn2.num_batches_tracked", "fc.weight", "fc.bias",
               "features.weight", "features.bias", "features.running_mean", "features.running_var", "features.num_batches_tracked")
@@ -141,11 +141,7 @@ class EmbeddingStage:
         return cls(sd, dropout, **kw)
 
     def to(self, device) -> "EmbeddingStage":
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("EmbeddingStage runs on a HIP device only (there is no CPU fallback)")
-        if dev.index is None:                                  # "cuda" names the current device; tensors carry its index
-            dev = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        dev = hip_device(device, "EmbeddingStage")
         _lib.load()
         self.t = {k: v.to(dev).contiguous() for k, v in self.t.items()}
         self.device = dev
@@ -299,53 +295,38 @@ def _lib_shapes_refused(b: int, ch: int, hw: int, n: int) -> bool:
     return not (ch % 64 == 0 and 64 <= ch <= 2048 and 1 <= hw <= 64 and n % 64 == 0 and 64 <= n <= 1024 and 1 <= b <= MAX_B)
 
 
-class StageSGD:
+class StageSGD(ClippedSGD):
     """The loop's `clip_grad_norm_(model.parameters(), max_norm)` and `opt_backbone.step()` (torch.optim.SGD, momentum, weight decay on
     every tensor) over the stage's five trainable tensors with one joint norm (idb_sgd_clip_step).  `lr` may be reassigned between
-    steps (the loop's scheduler: `learning_rate`)."""
+    steps (the loop's scheduler: `learning_rate`).  State dict: {"lr", "momentum", "weight_decay", "max_norm", "steps",
+    "momentum_buffers" ({name: fp32 on the host}, fc.weight in upstream's order; None before a step)}."""
 
     def __init__(self, stage: EmbeddingStage, lr: float, momentum: float = 0.9, weight_decay: float = 5e-4, max_norm: float = 5.0):
         if not isinstance(stage, EmbeddingStage):
             raise TypeError("StageSGD: stage must be an EmbeddingStage")
-        self.lr, self.momentum, self.weight_decay, self.max_norm = float(lr), float(momentum), float(weight_decay), float(max_norm)
-        if not (0.0 <= self.lr <= 1e4 and 0.0 <= self.momentum < 1.0 and 0.0 <= self.weight_decay <= 1e4 and 0.0 < self.max_norm <= 1e30):
-            raise ValueError("StageSGD: lr in [0, 1e4], momentum in [0, 1), weight_decay in [0, 1e4], max_norm in (0, 1e30]")
+        super().__init__(lr, momentum, weight_decay, max_norm)
         self.stage = stage
-        self.steps = 0
-        self._buf: Optional[Dict[str, torch.Tensor]] = None
 
-    def state_dict(self) -> Dict[str, object]:
-        """{"lr", "momentum", "weight_decay", "max_norm", "steps", "momentum_buffers" ({name: fp32 on the host}, fc.weight in upstream's
-        order; None before a step)}."""
+    def _new_buffers(self) -> Dict[str, torch.Tensor]:
+        return {k: torch.empty_like(self.stage.t[k]) for k in TRAINABLE}
+
+    def _buffers_out(self, bufs):
         st = self.stage
-        bufs = None
-        if self._buf is not None:
-            bufs = {k: v.detach().cpu().clone() for k, v in self._buf.items()}
-            bufs["fc.weight"] = to_upstream_order(bufs["fc.weight"], st.ch, st.hw)
-        return {"lr": self.lr, "momentum": self.momentum, "weight_decay": self.weight_decay, "max_norm": self.max_norm, "steps": self.steps,
-                "momentum_buffers": bufs}
+        return {k: to_upstream_order(v, st.ch, st.hw) if k == "fc.weight" else v.clone() for k, v in bufs.items()}
 
-    def load_state_dict(self, sd) -> None:
-        missing = [k for k in ("lr", "momentum", "weight_decay", "max_norm", "steps", "momentum_buffers") if k not in sd]
-        if missing:
-            raise ValueError(f"StageSGD state dict without {missing}")
-        bufs, steps, st = sd["momentum_buffers"], int(sd["steps"]), self.stage
-        if (bufs is None) != (steps == 0):
-            raise ValueError("StageSGD state dict: momentum buffers exist exactly after the first step")
-        new = None
-        if bufs is not None:
-            if sorted(bufs) != sorted(TRAINABLE):
-                raise ValueError(f"StageSGD state dict: momentum_buffers expected {sorted(TRAINABLE)}")
-            new = {}
-            for k in TRAINABLE:
-                v = bufs[k].detach().to(torch.float32)
-                want = (st.n, st.ch * st.hw) if k == "fc.weight" else tuple(st.t[k].shape)
-                if tuple(v.shape) != want:
-                    raise ValueError(f"StageSGD state dict: momentum buffer {k} expected {want}")
-                v = to_device_order(v, st.ch, st.hw) if k == "fc.weight" else v.contiguous().clone()
-                new[k] = v.to(st.device) if st.device is not None else v
-        self.lr, self.momentum, self.weight_decay, self.max_norm = (float(sd[k]) for k in ("lr", "momentum", "weight_decay", "max_norm"))
-        self.steps, self._buf = steps, new
+    def _buffers_in(self, bufs) -> Dict[str, torch.Tensor]:
+        st = self.stage
+        if sorted(bufs) != sorted(TRAINABLE):
+            raise ValueError(f"StageSGD state dict: momentum_buffers expected {sorted(TRAINABLE)}")
+        new = {}
+        for k in TRAINABLE:
+            v = bufs[k].detach().to(torch.float32)
+            want = (st.n, st.ch * st.hw) if k == "fc.weight" else tuple(st.t[k].shape)
+            if tuple(v.shape) != want:
+                raise ValueError(f"StageSGD state dict: momentum buffer {k} expected {want}")
+            v = to_device_order(v, st.ch, st.hw) if k == "fc.weight" else v.contiguous().clone()
+            new[k] = v.to(st.device) if st.device is not None else v
+        return new
 
     def step(self, grad: StageGrad) -> float:
         """One clipped SGD step on the five tensors.  Returns the joint gradient norm before clipping, as clip_grad_norm_ does."""
@@ -361,11 +342,7 @@ class StageSGD:
             if gs[k].dtype != torch.float32 or tuple(gs[k].shape) != tuple(st.t[k].shape) or gs[k].device != dev:
                 raise ValueError(f"StageSGD.step: gradient of {k} expected fp32 {tuple(st.t[k].shape)} on {dev}")
             gs[k] = gs[k].contiguous()
-        first = self._buf is None
-        if first:
-            self._buf = {k: torch.empty_like(st.t[k]) for k in TRAINABLE}
-        elif self._buf["fc.weight"].device != dev:
-            self._buf = {k: v.to(dev) for k, v in self._buf.items()}
+        first = self._begin(dev)
         n = len(TRAINABLE)
         arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])      # noqa: E731
         numel = (C.c_int64 * n)(*[st.t[k].numel() for k in TRAINABLE])
@@ -375,11 +352,21 @@ class StageSGD:
                                                  arr([self._buf[k] for k in TRAINABLE]), numel, self.lr, self.momentum, self.weight_decay,
                                                  self.max_norm, 1 if first else 0, total.data_ptr(), ws.data_ptr(),
                                                  _lib.IDB_SGD_CLIP_WS_BYTES, torch.cuda.current_stream(dev).cuda_stream), "idb_sgd_clip_step")
-        self.steps += 1
-        norm = float(total.item())
-        if not math.isfinite(norm):
-            raise ValueError(f"StageSGD.step: the gradient norm is not finite ({norm}); the step has been applied")
-        return norm
+        return self._finish(float(total.item()))
+
+
+def loss_backward(stage: EmbeddingStage, header: MarginHeader, out: StageOut, labels) -> Tuple[HeadLoss, HeadGrad, StageGrad]:
+    """The loop's lines between the model and the optimisers (train_FR.py:280-290): the header's loss and gradients on the stage's
+    unit rows, then the stage's backward.  AdaFace follows the loop's literal lines (`norm = torch.norm(features, 2, 1, True)`,
+    `torch.div(features, norm)`), so the cotangent passes the second projection (renormalised=True)."""
+    features = out.embeddings
+    ada = header.loss_name == "AdaFace"
+    if ada:
+        norm = torch.norm(features, 2, 1, True)
+        hl, hg = header.loss_and_grad(torch.div(features, norm), labels, norms=norm)
+    else:
+        hl, hg = header.loss_and_grad(features, labels)
+    return hl, hg, stage.backward(out, hg.embeddings, renormalised=ada)
 
 
 def train_step(stage: EmbeddingStage, header: MarginHeader, opt_stage: StageSGD, opt_header: HeaderSGD, feature_map, labels, keep=None,
@@ -394,15 +381,7 @@ def train_step(stage: EmbeddingStage, header: MarginHeader, opt_stage: StageSGD,
         raise TypeError("train_step: expected a MarginHeader and the HeaderSGD built on it")
     if not stage.training:
         raise ValueError("train_step: the stage is in eval mode")
-    out = stage(feature_map, keep=keep, generator=generator)
-    features = out.embeddings
-    ada = header.loss_name == "AdaFace"
-    if ada:
-        norm = torch.norm(features, 2, 1, True)
-        hl, hg = header.loss_and_grad(torch.div(features, norm), labels, norms=norm)
-    else:
-        hl, hg = header.loss_and_grad(features, labels)
-    grad = stage.backward(out, hg.embeddings, renormalised=ada)
+    hl, hg, grad = loss_backward(stage, header, stage(feature_map, keep=keep, generator=generator), labels)
     norm_stage = opt_stage.step(grad)
     norm_header = opt_header.step(hg.kernel)
     return {"loss": hl.loss, "acc": hl.acc, "correct": hl.correct, "grad_norm_stage": norm_stage, "grad_norm_header": norm_header,

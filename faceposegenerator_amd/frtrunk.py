@@ -18,21 +18,20 @@ statistics and batch counters are then left as they were), shapes outside the ke
 from __future__ import annotations
 
 import ctypes as C
-import math
 from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib
-from .arcface import ARCHS, PLANES
+from ._frtrain import ClippedSGD, hip_device
+from .arcface import _BN, ARCHS, PLANES, trunk_param_shapes
 from .frhead import HeaderSGD, MarginHeader
 from .frtail import TRAINABLE as STAGE_TRAINABLE
-from .frtail import EmbeddingStage, StageGrad, to_device_order, to_upstream_order
+from .frtail import EmbeddingStage, StageGrad, loss_backward, to_device_order, to_upstream_order
 
 EPS, MOMENTUM = 1e-5, 0.1
 MAX_B, MAX_HW, MAX_C = 1024, 128, 2048
-_BN = ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")
 
 
 def conv_to_device(w: torch.Tensor) -> torch.Tensor:
@@ -42,35 +41,6 @@ def conv_to_device(w: torch.Tensor) -> torch.Tensor:
 
 def conv_to_upstream(w: torch.Tensor) -> torch.Tensor:
     return w.permute(0, 3, 1, 2).contiguous()
-
-
-def trunk_param_shapes(layers: Sequence[int]) -> "OrderedDict[str, Tuple[int, ...]]":
-    """Key names and shapes of the trunk (everything of ``arcface.param_shapes`` in front of ``bn2``) for a list of block counts."""
-    out: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
-
-    def bn(key, c):
-        for f in _BN:
-            out[f"{key}.{f}"] = () if f == "num_batches_tracked" else (c,)
-
-    out["conv1.weight"] = (64, 3, 3, 3)
-    bn("bn1", 64)
-    out["prelu.weight"] = (64,)
-    cin = 64
-    for i, (nb, planes) in enumerate(zip(layers, PLANES)):
-        for j in range(nb):
-            k = f"layer{i + 1}.{j}"
-            c = cin if j == 0 else planes
-            bn(f"{k}.bn1", c)
-            out[f"{k}.conv1.weight"] = (planes, c, 3, 3)
-            bn(f"{k}.bn2", planes)
-            out[f"{k}.prelu.weight"] = (planes,)
-            out[f"{k}.conv2.weight"] = (planes, planes, 3, 3)
-            bn(f"{k}.bn3", planes)
-            if j == 0:
-                out[f"{k}.downsample.0.weight"] = (planes, c, 1, 1)
-                bn(f"{k}.downsample.1", planes)
-        cin = planes
-    return out
 
 
 def _is_buffer(key: str) -> bool:
@@ -86,12 +56,7 @@ def _refuse_unbuilt(sd, what: str) -> None:
 
 
 def _device(device) -> torch.device:
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("the trunk runs on a HIP device only (there is no CPU fallback)")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
-    return dev
+    return hip_device(device, "the trunk")
 
 
 def _stream(dev) -> int:
@@ -576,66 +541,45 @@ class Trunk:
         return {k: got[k] for k in self.trainable()}
 
 
-class BackboneSGD:
+class BackboneSGD(ClippedSGD):
     """The loop's `clip_grad_norm_(model.parameters(), max_norm)` and `opt_backbone.step()` over every trainable tensor of trunk and
     stage in upstream's model.parameters() order, with one joint norm (idb_sgd_clip_step_table).  `lr` may be reassigned between
-    steps (frtail.learning_rate)."""
+    steps (frtail.learning_rate).  State dict: {"lr", "momentum", "weight_decay", "max_norm", "steps", "momentum_buffers" ({key: fp32
+    on the host} in upstream's layouts; None before a step)}."""
 
     def __init__(self, trunk: Trunk, stage: EmbeddingStage, lr: float, momentum: float = 0.9, weight_decay: float = 5e-4, max_norm: float = 5.0):
         if not isinstance(trunk, Trunk) or not isinstance(stage, EmbeddingStage):
             raise TypeError("BackboneSGD: expected a Trunk and an EmbeddingStage")
-        self.lr, self.momentum, self.weight_decay, self.max_norm = float(lr), float(momentum), float(weight_decay), float(max_norm)
-        if not (0.0 <= self.lr <= 1e4 and 0.0 <= self.momentum < 1.0 and 0.0 <= self.weight_decay <= 1e4 and 0.0 < self.max_norm <= 1e30):
-            raise ValueError("BackboneSGD: lr in [0, 1e4], momentum in [0, 1), weight_decay in [0, 1e4], max_norm in (0, 1e30]")
+        super().__init__(lr, momentum, weight_decay, max_norm)
         self.trunk, self.stage = trunk, stage
         self.keys: List[str] = trunk.trainable() + list(STAGE_TRAINABLE)
         if len(self.keys) > 1024:
             raise ValueError(f"BackboneSGD: {len(self.keys)} tensors, idb_sgd_clip_step_table takes at most 1024")
-        self.steps = 0
-        self._buf: Optional[Dict[str, torch.Tensor]] = None
         self._tables = None
 
     def _weight(self, key: str) -> torch.Tensor:
         return self.stage.t[key] if key in STAGE_TRAINABLE else self.trunk.tensor(key)
 
-    def _to_upstream(self, key: str, v: torch.Tensor) -> torch.Tensor:
-        if key == "fc.weight":
-            return to_upstream_order(v, self.stage.ch, self.stage.hw)
-        return conv_to_upstream(v) if v.ndim == 4 else v.clone()
+    def _new_buffers(self) -> Dict[str, torch.Tensor]:
+        return {k: torch.empty_like(self._weight(k)) for k in self.keys}
 
-    def _to_device_layout(self, key: str, v: torch.Tensor) -> torch.Tensor:
-        if key == "fc.weight":
-            return to_device_order(v, self.stage.ch, self.stage.hw)
-        return conv_to_device(v) if v.ndim == 4 else v.contiguous().clone()
+    def _buffers_out(self, bufs):
+        st = self.stage
+        return {k: to_upstream_order(v, st.ch, st.hw) if k == "fc.weight" else conv_to_upstream(v) if v.ndim == 4 else v.clone()
+                for k, v in bufs.items()}
 
-    def state_dict(self) -> Dict[str, object]:
-        """{"lr", "momentum", "weight_decay", "max_norm", "steps", "momentum_buffers" ({key: fp32 on the host} in upstream's layouts;
-        None before a step)}."""
-        bufs = None
-        if self._buf is not None:
-            bufs = {k: self._to_upstream(k, v.detach().cpu()) for k, v in self._buf.items()}
-        return {"lr": self.lr, "momentum": self.momentum, "weight_decay": self.weight_decay, "max_norm": self.max_norm, "steps": self.steps,
-                "momentum_buffers": bufs}
-
-    def load_state_dict(self, sd) -> None:
-        missing = [k for k in ("lr", "momentum", "weight_decay", "max_norm", "steps", "momentum_buffers") if k not in sd]
-        if missing:
-            raise ValueError(f"BackboneSGD state dict without {missing}")
-        bufs, steps = sd["momentum_buffers"], int(sd["steps"])
-        if (bufs is None) != (steps == 0):
-            raise ValueError("BackboneSGD state dict: momentum buffers exist exactly after the first step")
-        new = None
-        if bufs is not None:
-            if sorted(bufs) != sorted(self.keys):
-                raise ValueError("BackboneSGD state dict: momentum_buffers do not match the backbone's trainable tensors")
-            new = {}
-            for k in self.keys:
-                v = self._to_device_layout(k, bufs[k].detach().to("cpu", torch.float32))
-                if tuple(v.shape) != tuple(self._weight(k).shape):
-                    raise ValueError(f"BackboneSGD state dict: momentum buffer {k} has the wrong shape")
-                new[k] = v.to(self.trunk.device) if self.trunk.device is not None else v
-        self.lr, self.momentum, self.weight_decay, self.max_norm = (float(sd[k]) for k in ("lr", "momentum", "weight_decay", "max_norm"))
-        self.steps, self._buf, self._tables = steps, new, None
+    def _buffers_in(self, bufs) -> Dict[str, torch.Tensor]:
+        if sorted(bufs) != sorted(self.keys):
+            raise ValueError("BackboneSGD state dict: momentum_buffers do not match the backbone's trainable tensors")
+        st, new = self.stage, {}
+        for k in self.keys:
+            v = bufs[k].detach().to("cpu", torch.float32)
+            v = to_device_order(v, st.ch, st.hw) if k == "fc.weight" else conv_to_device(v) if v.ndim == 4 else v.contiguous().clone()
+            if tuple(v.shape) != tuple(self._weight(k).shape):
+                raise ValueError(f"BackboneSGD state dict: momentum buffer {k} has the wrong shape")
+            new[k] = v.to(self.trunk.device) if self.trunk.device is not None else v
+        self._tables = None
+        return new
 
     def step(self, trunk_grads: Dict[str, torch.Tensor], stage_grad: StageGrad) -> float:
         """One clipped SGD step on every tensor.  Returns the joint gradient norm before clipping, as clip_grad_norm_ does."""
@@ -654,15 +598,13 @@ class BackboneSGD:
             if g is None or g.dtype != torch.float32 or tuple(g.shape) != tuple(w.shape) or g.device != dev:
                 raise ValueError(f"BackboneSGD.step: gradient of {k} expected fp32 {tuple(w.shape)} on {dev}")
             grads.append(g.contiguous())
-        first = self._buf is None
+        first = self._begin(dev)
         if first:
-            self._buf = {k: torch.empty_like(w) for k, w in zip(self.keys, ws_)}
             self._tables = None
         n = len(self.keys)
         i64 = lambda vals: torch.tensor(vals, dtype=torch.int64).to(dev)      # noqa: E731
         if self._tables is None or self._tables[3] != [w.data_ptr() for w in ws_]:
-            bufs = [self._buf[k] if self._buf[k].device == dev else self._buf[k].to(dev) for k in self.keys]
-            self._buf = dict(zip(self.keys, bufs))
+            bufs = [self._buf[k] for k in self.keys]
             self._tables = (i64([w.data_ptr() for w in ws_]), i64([b.data_ptr() for b in bufs]), i64([w.numel() for w in ws_]),
                             [w.data_ptr() for w in ws_])
         tw, tb, tn, _ = self._tables
@@ -674,11 +616,7 @@ class BackboneSGD:
         _lib.check(lib.idb_sgd_clip_step_table(n, tw.data_ptr(), tg.data_ptr(), tb.data_ptr(), tn.data_ptr(), self.lr, self.momentum,
                                                self.weight_decay, self.max_norm, 1 if first else 0, total.data_ptr(), ws.data_ptr(), need,
                                                _stream(dev)), "idb_sgd_clip_step_table")
-        self.steps += 1
-        norm = float(total.item())
-        if not math.isfinite(norm):
-            raise ValueError(f"BackboneSGD.step: the gradient norm is not finite ({norm}); the step has been applied")
-        return norm
+        return self._finish(float(total.item()))
 
 
 def train_step_full(trunk: Trunk, stage: EmbeddingStage, header: MarginHeader, opt_backbone: BackboneSGD, opt_header: HeaderSGD, images, labels,
@@ -697,15 +635,7 @@ def train_step_full(trunk: Trunk, stage: EmbeddingStage, header: MarginHeader, o
     if not trunk.training or not stage.training:
         raise ValueError("train_step_full: the trunk or the stage is in eval mode")
     tout = trunk(images)
-    out = stage(tout.map, keep=keep, generator=generator)
-    features = out.embeddings
-    ada = header.loss_name == "AdaFace"
-    if ada:
-        norm = torch.norm(features, 2, 1, True)
-        hl, hg = header.loss_and_grad(torch.div(features, norm), labels, norms=norm)
-    else:
-        hl, hg = header.loss_and_grad(features, labels)
-    grad = stage.backward(out, hg.embeddings, renormalised=ada)
+    hl, hg, grad = loss_backward(stage, header, stage(tout.map, keep=keep, generator=generator), labels)
     tgrads = trunk.backward(tout, grad.input)
     norm_backbone = opt_backbone.step(tgrads, grad)
     norm_header = opt_header.step(hg.kernel)

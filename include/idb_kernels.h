@@ -777,7 +777,8 @@ int idb_head_logits(const idb_head_desc* h, float* thetas, double* rows, void* w
  *       dX merge + projection, dW tiles + projection.  grad_rows: double [3][b]: the target's slope d_i with its clamp / clip mask
  *       folded in (not finite for an ArcFace target cosine of +-1 exactly: callers refuse), that mask, |e_i|.  d_emb: fp32 [b][d].
  *       d_kernel: fp32 [d][c], as torch stores kernel.grad.  Arguments as idb_head_loss; IDB_EUNSUPPORTED past the partials' limit.
- *   idb_head_sgd_step: total_norm = |grad|_2 (double, fixed order; written to total_norm [1] on the device),
+ *   idb_head_sgd_step: the clipped SGD step all three entries share (its arithmetic: csrc/idb_sgd.h), here on the kernel alone:
+ *       total_norm = |grad|_2 (double, fixed order; written to total_norm [1] on the device),
  *       coef = min(1, max_norm / (total_norm + 1e-6)), g = coef grad + weight_decay kernel, momentum_buf = g on the first step, else
  *       momentum momentum_buf + g, kernel -= lr momentum_buf (each element in double, each fp32 state rounded once), then
  *       idb_head_pack(kernel, ...) so that wn / col_norm / bad_cols follow the kernel.  kernel, grad, momentum_buf: fp32 [d][c].
@@ -891,7 +892,7 @@ int idb_sgd_clip_step(int32_t count, float* const* weights, const float* const* 
  *       id_affine: the stem's activation and the block's residual in one elementwise launch.
  *   idb_blk_pack_images: float NCHW [b][3][h][w] -> NHWC [b][h][w][4], the fourth channel 0.
  *   idb_sgd_clip_step_table: idb_sgd_clip_step over 1..1024 tensors whose pointer and numel tables (count entries each) lie in
- *       DEVICE memory; the same arithmetic and summation order, bit-identical to idb_sgd_clip_step for up to 8 tensors.  The tables'
+ *       DEVICE memory; the same kernels on the same geometry, bit-identical to idb_sgd_clip_step for up to 8 tensors (csrc/idb_sgd.hip).  The tables'
  *       contents cannot be validated on the host: the caller guarantees 1 <= numel <= 2^32 and distinct buffers.
  *       ws: idb_sgd_clip_table_workspace_bytes(count), 16-byte aligned.
  * ------------------------------------------------------------------------------------------ */

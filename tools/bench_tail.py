@@ -3,7 +3,7 @@
 7 x 7 x 512 through bn2 -> dropout -> fc (25 088 -> 512) -> features -> F.normalize, backward, and the clipped SGD step.  Columns:
   forward     stage(feature_map, keep)                            (idb_tail_forward)
   backward    stage.backward(out, g)                              (idb_tail_backward)
-  sgd         StageSGD.step(grad)                                 (idb_sgd_clip_step)
+  sgd         StageSGD.step(grad)                                 (idb_sgd_clip_step, csrc/idb_sgd.hip)
   train_step  frtail.train_step with a CosFace header of --classes identities (both backwards, both optimiser steps)
   torch_*     a plain fp32 eager restatement on the same GPU, written here: nn.BatchNorm2d -> flatten -> x * keep / (1 - p) ->
               nn.Linear -> nn.BatchNorm1d (weight frozen) -> F.normalize, autograd's backward(), clip_grad_norm_ + torch.optim.SGD
