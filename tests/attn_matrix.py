@@ -42,6 +42,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from faceposegenerator_amd import _lib as L
+from matrix_common import check_t as check  # noqa: F401  (the torch verdict, re-exported to the two test files)
 
 UNIT = {"bf16": 2.0 ** -8, "f16": 2.0 ** -11}
 TDT = {"bf16": torch.bfloat16, "f16": torch.float16}
@@ -441,17 +442,6 @@ def bound(r: Ref, n_kv: int, dtype: str, recipe: str) -> torch.Tensor:
 
 def expected(inp: Inputs, r: Ref, recipe: str) -> torch.Tensor:
     return inp.exact.to(r.ref.device) if recipe in EXACT else r.ref
-
-
-def check(out: torch.Tensor, want: torch.Tensor, bnd: torch.Tensor) -> Tuple[bool, float, int]:
-    """(every element finite and within its bound, worst err / bound, number of failing elements).  An element whose bound is 0 must
-    be exact (ratio inf otherwise); none is skipped."""
-    out = out.double()
-    err = (out - want).abs()
-    bad = ~torch.isfinite(out) | ~(err <= bnd)
-    ratio = torch.where(bnd > 0, err / bnd.clamp(min=1e-300), torch.where(err > 0, torch.full_like(err, math.inf), torch.zeros_like(err)))
-    ratio = torch.where(torch.isfinite(out), torch.nan_to_num(ratio, nan=math.inf), torch.full_like(ratio, math.inf))
-    return not bool(bad.any()), float(ratio.max()), int(bad.sum())
 
 
 def old_criterion(out: torch.Tensor, ref: torch.Tensor, dtype: str) -> Tuple[bool, float, float]:

@@ -46,9 +46,8 @@ import numpy as np
 
 import frblock_oracle as BO
 import frtail_oracle as TO
-from stem_matrix import GUARD, NAN32, check, describe, fma32  # noqa: F401  (re-exported to the two test files)
+from matrix_common import F32, F64, GUARD, NAN32, check, describe, fma32  # noqa: F401  (re-exported to the two test files)
 
-F32, F64 = np.float32, np.float64
 U32, U64, SECOND = TO.U32, TO.U64, TO.SECOND
 TM, TK, FILL, MAX_WSLICES, MAX_SSLICES = 128, 32, 256, 64, 1024
 

@@ -1,7 +1,7 @@
 """The test matrix of the MTCNN detector kernels (csrc/idb_mtcnn.hip: idb_crop_resize_area_u8, idb_conv2d_f32, idb_maxpool2d_f32,
 idb_softmax_pairs_f32, idb_nms_mask), shared by test_detect_matrix_cpu.py (references against torch, criteria, teeth, argument checks) and
 test_detect_matrix_gpu.py (launch + compare): cases, input recipes, float64 references written from the definitions, emulations of the
-kernels' fp32 arithmetic, injectable defects and the element-wise criteria.  numpy only: no torch, no GPU.
+kernels' fp32 arithmetic, injectable defects and the bounds; the verdicts are matrix_common.py's.  numpy only, no GPU.
 
 Criteria (u = 2^-24, derived from the arithmetic, no constant was tuned):
 
@@ -37,60 +37,17 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 from numpy.lib.stride_tricks import sliding_window_view
 
-U = 2.0 ** -24
-F32 = np.float32
+from matrix_common import F32, GUARD, NAN32, U, bit_equal, check, describe, gamma, ulp32  # noqa: F401  (re-exported to the two test files)
+
 UNDECIDED_CAP = 0.01
 THR_P, THR_RO = 0.6, 0.7              # P-Net keeps p >= 0.6, R- and O-Net keep p > 0.7
 SUB, MUL = 127.5, 0.0078125           # the detector's normalisation: (x - 127.5) / 128
-GUARD = 64                            # guard elements on each side of every output buffer
-NAN_BITS = 0x7FC0DE7C                 # the guards' fp32 pattern (a quiet NaN with a payload)
 WORD_GUARD = 0xDEADBEEFCAFEF00D       # the guards' pattern around the uint64 mask
-
-
-def gamma(n: int) -> float:
-    return n * U / (1.0 - n * U)
 
 
 def thresholds() -> Tuple[float, float]:
     """The thresholds as the host applies them: `prob_np >= 0.6` on an fp32 array compares in fp32."""
     return float(F32(THR_P)), float(F32(THR_RO))
-
-
-def ulp32(v) -> np.ndarray:
-    """fp32 spacing at |v| (v float64): 2^-149 below the normal range and at 0."""
-    return np.spacing(np.abs(np.asarray(v, np.float64)).astype(F32)).astype(np.float64)
-
-
-def check(got, want, bound) -> Tuple[bool, float, Tuple[int, ...], float, float]:
-    """(every element finite and within its bound, worst err / bound, its index, its error, its bound); a zero bound demands equality."""
-    got, want, bound = np.asarray(got, np.float64), np.asarray(want, np.float64), np.asarray(bound, np.float64)
-    if got.shape != want.shape:
-        return False, np.inf, (), np.inf, 0.0
-    if got.size == 0:
-        return True, 0.0, (), 0.0, 0.0
-    with np.errstate(invalid="ignore", divide="ignore"):
-        err = np.abs(got - want)
-        ratio = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err > 0, np.inf, 0.0))
-    ratio = np.where(np.isfinite(got) & np.isfinite(err), ratio, np.inf)
-    i = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
-    ok = bool(np.all(np.isfinite(got)) and np.all(err <= bound))
-    return ok, float(ratio[i]), tuple(int(v) for v in i), float(err[i]), float(bound[i])
-
-
-def bit_equal(got, want) -> Tuple[bool, Tuple[int, ...]]:
-    """fp32 arrays equal bit for bit (so -inf equals -inf and a NaN pattern only itself); the first differing index."""
-    got, want = np.ascontiguousarray(got, F32), np.ascontiguousarray(want, F32)
-    if got.shape != want.shape:
-        return False, ()
-    d = got.view(np.uint32) != want.view(np.uint32)
-    if not d.any():
-        return True, ()
-    return False, tuple(int(v) for v in np.argwhere(d)[0])
-
-
-def describe(name, res) -> str:
-    ok, ratio, idx, err, bound = res
-    return f"{name}: worst element {idx}: |err| {err:.6e}, bound {bound:.6e}, err / bound {ratio:.4f}"
 
 
 def decisions(got32, ref64, bound, thr_index: int):

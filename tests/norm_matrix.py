@@ -59,6 +59,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from faceposegenerator_amd import _lib as L
+from matrix_common import check_t as check  # noqa: F401  (the torch verdict, re-exported to the two test files)
 
 UNIT = {"bf16": 2.0 ** -8, "f16": 2.0 ** -11}
 TDT = {"bf16": torch.bfloat16, "f16": torch.float16}
@@ -516,16 +517,6 @@ def gn_partial_sums(x, p: Plan, groups):
     want = torch.stack([xg.sum(dim=(2, 4)), (xg * xg).sum(dim=(2, 4))], -1)
     mag = torch.stack([xg.abs().sum(dim=(2, 4)), (xg * xg).sum(dim=(2, 4))], -1)
     return want, mag
-
-
-def check(out, want, bnd) -> Tuple[bool, float, int]:
-    """(every element finite and within its bound, worst err / bound, number of failing elements); a zero bound demands equality."""
-    out = out.double()
-    err = (out - want).abs()
-    bad = ~torch.isfinite(out) | ~(err <= bnd)
-    ratio = torch.where(bnd > 0, err / bnd.clamp(min=1e-300), torch.where(err > 0, torch.full_like(err, math.inf), torch.zeros_like(err)))
-    ratio = torch.where(torch.isfinite(out), torch.nan_to_num(ratio, nan=math.inf), torch.full_like(ratio, math.inf))
-    return not bool(bad.any()), float(ratio.max()), int(bad.sum())
 
 
 def old_criterion(out, ref, dtype, scale=1.0) -> bool:

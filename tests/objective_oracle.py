@@ -12,14 +12,11 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from matrix_common import ulp32  # noqa: F401  (used here and by the objective tests)
+
 U32 = 2.0 ** -24
 MTCNN_IMAGE_SEED = 23         # the float test image of the detector test (2 x 80 x 96): of the seeds 1..24 the one whose oracle run stays
                               # furthest (7.6e-4) from every stage threshold; test_objective_cpu.py asserts the margin
-
-
-def ulp32(v) -> np.ndarray:
-    """fp32 spacing at |v| (v float64)."""
-    return np.spacing(np.abs(np.asarray(v, np.float64)).astype(np.float32)).astype(np.float64)
 
 
 # ---- schedule -----------------------------------------------------------------------------------------------------------------------

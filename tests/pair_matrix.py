@@ -1,7 +1,7 @@
 """The test matrix of the all-pairs metric kernels (csrc/idb_pair.hip: idb_pair_dist2, idb_pair_knn_radii, idb_pair_prdc_counts,
 idb_pair_nearest, idb_pair_poly_sums), shared by test_pair_matrix_cpu.py (conditions on the inputs, teeth, argument checks) and
 test_pair_matrix_gpu.py (launch through the C ABI + compare): cases, input recipes, the float64 references of tests/metrics_oracle.py, an
-fp32 restatement of the kernels, injectable defects and the criteria.  numpy only: no torch, no GPU.
+fp32 restatement of the kernels, injectable defects and the criteria (the verdict `within` is matrix_common.py's).  numpy only, no GPU.
 
 Criteria (every number is metrics_oracle's or follows from the arithmetic, none was tuned):
 
@@ -34,17 +34,14 @@ from typing import Callable, Dict, Optional, Tuple
 import numpy as np
 
 import metrics_oracle as O
+from matrix_common import F32, GUARD, NAN32, NAN64, within  # noqa: F401  (re-exported to the two test files)
 
-F32 = np.float32
 TAU = O.TAU
 UNDECIDED_CAP = O.UNDECIDED_CAP
 PT = 128                              # rows of a block
 PK = 32                               # K per stage
 MAX_SPLITS = 8
 KNN_MAX = 8
-GUARD = 64                            # guard elements on each side of every output buffer
-NAN_BITS = 0x7FC0DE7C                 # the guards' 4-byte pattern: a quiet fp32 NaN with a payload, a large positive int32
-NAN_BITS64 = 0x7FF8C0DE7C0DE7C0       # the guards' 8-byte pattern: a quiet float64 NaN
 INT_MAX = 0x7FFFFFFF
 INF_BITS = 0x7F800000
 
@@ -361,9 +358,9 @@ def emulate_prdc(real, gen, shift, r2_real, r2_gen, vec=None, defect=None):
     nr, ng = d.shape
     r2_real, r2_gen = np.asarray(r2_real, F32), np.asarray(r2_gen, F32)
     reach = min(nr, ng) if defect == "init_min" else max(nr, ng)
-    inside = np.where(np.arange(ng) < reach, 0, NAN_BITS).astype(np.int64) + (d < r2_real[:, None]).sum(axis=0)
-    covered = np.where(np.arange(nr) < reach, 0, NAN_BITS).astype(np.int64) | (d < r2_gen[None, :]).any(axis=1)
-    bits = np.minimum(np.where(np.arange(nr) < reach, INF_BITS, NAN_BITS).astype(np.uint32), d.min(axis=1).view(np.uint32))
+    inside = np.where(np.arange(ng) < reach, 0, NAN32).astype(np.int64) + (d < r2_real[:, None]).sum(axis=0)
+    covered = np.where(np.arange(nr) < reach, 0, NAN32).astype(np.int64) | (d < r2_gen[None, :]).any(axis=1)
+    bits = np.minimum(np.where(np.arange(nr) < reach, INF_BITS, NAN32).astype(np.uint32), d.min(axis=1).view(np.uint32))
     return inside.astype(np.int32), covered.astype(np.int32), bits.view(F32)
 
 
@@ -390,20 +387,6 @@ def emulate_poly(x, y, ix, iy, gamma=1.0, coef0=1.0, defect=None) -> np.ndarray:
 
 
 # ---- criteria --------------------------------------------------------------------------------------------------------------------------
-def within(what: str, got, want, bound):
-    """AssertionError naming the worst element unless every one is finite and within its bound; returns worst err / bound."""
-    got, want, bound = np.asarray(got, np.float64), np.asarray(want, np.float64), np.asarray(bound, np.float64)
-    assert got.shape == want.shape, f"{what}: shape {got.shape}, expected {want.shape}"
-    with np.errstate(invalid="ignore", divide="ignore"):
-        err = np.abs(got - want)
-        ratio = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err > 0, np.inf, 0.0))
-    ratio = np.where(np.isfinite(got) & np.isfinite(err), ratio, np.inf)
-    i = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
-    assert ratio[i] <= 1.0, (f"{what}: element {tuple(int(v) for v in i)} is {got[i]!r}, float64 has {want[i]!r}: error {err[i]:.3e}, "
-                             f"bound {bound[i]:.3e}")
-    return float(ratio[i])
-
-
 def judge_dist2(what: str, got, want, scale) -> float:
     ratio = within(what, got, want, TAU * scale)
     assert (np.asarray(got) >= 0).all() and not np.signbit(got).any(), f"{what}: a negative distance or -0"
@@ -457,13 +440,8 @@ def judge_auth(what: str, ref: O.Auth, rr_min, rg_min, rg_arg) -> None:
 
 
 def judge_exact(what: str, got, want) -> float:
-    """Integer cases: the float64 answer bit for bit (as values: both are exact)."""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, f"{what}: shape {got.shape}, expected {want.shape}"
-    bad = np.argwhere(~(got.astype(np.float64) == want.astype(np.float64)))
-    assert bad.size == 0, (f"{what}: element {bad[0].tolist()} is {got[tuple(bad[0])]!r}, exact value {want[tuple(bad[0])]!r}: error "
-                           f"{abs(float(got[tuple(bad[0])]) - float(want[tuple(bad[0])])):.3e}, bound 0")
-    return 0.0
+    """Integer cases: the float64 answer, as values (both are exact): a bound of 0."""
+    return within(what, got, want, 0.0)
 
 
 def exact_dist_precondition(a, b) -> float:

@@ -3,14 +3,15 @@ idb_pack_matrix, idb_pack_matrix_scaled, idb_lora_merge, idb_lora_merge_scaled, 
 idb_vae_sample, idb_postprocess, idb_cast_f32, idb_nhwc_to_nchw_f32, idb_f32_nhwc_to_nchw and idb_embed_tokens.  Shared by
 test_prep_matrix_cpu.py (recipes, teeth, emulations, argument checks) and test_prep_matrix_gpu.py (launch + compare): cases at the smallest
 shapes that can go wrong, input recipes from fixed seeds, float64 references written from the definitions, numpy float32 emulations of the
-kernels' arithmetic, injectable defects and the element-wise criteria.  numpy only: no torch, no GPU.  The helpers (gamma, check, describe,
-to_bits, from_bits, round_T, bf16_bits, fma32, _t_bound, U_T, SUB_T, GUARD, NAN32, NAN16) are stem_matrix.py's.
+kernels' arithmetic, injectable defects and the element-wise criteria.  numpy only, no GPU.  The helpers (gamma, check, describe, to_bits,
+from_bits, round_T, bf16_bits, fma32, U_T, SUB_T, GUARD, NAN32, NAN16) are matrix_common.py's; the emulations' fmaf (_fma), the keyed
+generator (_rng) and the bound of a rounding to T (_t_bound) are stem_matrix.py's, whose recipes they were written for.
 
 Every kernel but ln_fold_vectors runs one thread per element (tile_weight, embed_tokens: per 16-byte chunk / four features) in 256-thread
 blocks, so every family has a single element, a total below 256 and a ragged second block (tile_weight's chunk count is a multiple of
 128: one half block, one whole block, several).  ln_fold_vectors runs one wave per row, four rows per block.
 
-Criteria, per element.  u = 2^-24, gamma_n = n u / (1 - n u), u_T and sub_T as in stem_matrix.py.  Every count is read off the kernel.
+Criteria, per element.  u = 2^-24, gamma_n = n u / (1 - n u), u_T and sub_T as in matrix_common.py.  Every count is read off the kernel.
 
   bit-equal      pack_conv_weight, pack_matrix, cast_f32: one rounding to nearest even of the fp32 source [1], against round_T.  Both
                  transposes (no arithmetic), tile_weight (a copy; the rows past n are zeros), postprocess, vae_sample's mean (a copy)
@@ -63,8 +64,9 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from stem_matrix import (DTYPES, F32, F64, GUARD, NAN16, NAN32, SUB_T, U, U_T, _fma, _rng, _t_bound, bf16_bits, check, describe,  # noqa: F401
-                         fma32, from_bits, gamma, round_T, to_bits)
+from matrix_common import (DTYPES, F32, F64, GUARD, NAN16, NAN32, SUB_T, U, U_T, bf16_bits, check, describe, fma32, from_bits,  # noqa: F401
+                           gamma, round_T, to_bits)                            # re-exported to the two test files
+from stem_matrix import _fma, _rng, _t_bound
 
 ELEMENT_LIMIT = 1 << 39               # idb_misc.hip below_2p39: blocks_for returns unsigned, 2^31 blocks of 256
 

@@ -2,7 +2,7 @@
 idb_arcface_stem, idb_arcface_head (csrc/idb_arcface.hip), idb_pose_stem and idb_pose_head (csrc/idb_pose.hip).  Shared by
 test_stem_matrix_cpu.py (references against torch, recipes, teeth, argument checks) and test_stem_matrix_gpu.py (launch + compare): cases,
 input recipes from fixed seeds, float64 references written from the definitions, numpy float32 emulations of the kernels' arithmetic in the
-kernels' order, injectable defects and the element-wise criteria.  numpy only: no torch, no GPU.
+kernels' order, injectable defects and the bounds; the verdicts and the 16-bit conversions are matrix_common.py's.  numpy only, no GPU.
 
 Criteria.  u = 2^-24, gamma_n = n u / (1 - n u) (forward bound of n fp32 roundings on one term of a sum), u_T = 2^-11 (f16) or 2^-8
 (bf16).  Every count below is read off the kernel source; no constant is tuned.
@@ -52,89 +52,12 @@ from typing import List, Tuple
 import numpy as np
 from numpy.lib.stride_tricks import sliding_window_view
 
-U = 2.0 ** -24
-F32 = np.float32
-F64 = np.float64
-DTYPES = ("f16", "bf16")
-U_T = {"f16": 2.0 ** -11, "bf16": 2.0 ** -8}
-SUB_T = {"f16": 2.0 ** -25, "bf16": 0.0}
-GUARD = 64                            # guard elements on each side of every output buffer and of the head's workspace
-NAN32 = 0x7FC0DE7C                    # the fp32 guards' and pre-fill's pattern (a quiet NaN with a payload, as detect_matrix.NAN_BITS)
-NAN16 = 0x7FDE                        # 16 bits that are a NaN with a payload both as f16 and as bf16
+from matrix_common import (DTYPES, F32, F64, GUARD, NAN16, NAN32, SUB_T, U, U_T, bf16_bits, check, describe, fma32, from_bits,  # noqa: F401
+                           gamma, round_T, to_bits, ulp32)                     # re-exported to the two test files
+
 IN_SCALES = (1.0, 1.0 / 0.18215)
 TIMESTEPS = (0.0, 1.0, 34.0, 925.0, 958.0, 999.0)
 POSE_MEAN, POSE_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
-
-
-def gamma(n: int) -> float:
-    return n * U / (1.0 - n * U)
-
-
-def ulp32(v) -> np.ndarray:
-    return np.spacing(np.abs(np.asarray(v, F64)).astype(F32)).astype(F64)
-
-
-def check(got, want, bound) -> Tuple[bool, float, Tuple[int, ...], float, float]:
-    """(every element finite and within its bound, worst err / bound, its index, its error, its bound); a zero bound demands equality."""
-    got, want = np.asarray(got, F64), np.asarray(want, F64)
-    bound = np.broadcast_to(np.asarray(bound, F64), want.shape)
-    if got.shape != want.shape:
-        return False, np.inf, (), np.inf, 0.0
-    if got.size == 0:
-        return True, 0.0, (), 0.0, 0.0
-    with np.errstate(invalid="ignore", divide="ignore"):
-        err = np.abs(got - want)
-        ratio = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err > 0, np.inf, 0.0))
-    ratio = np.where(np.isfinite(got) & np.isfinite(err), ratio, np.inf)
-    i = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
-    ok = bool(np.all(np.isfinite(got)) and np.all(err <= bound))
-    return ok, float(ratio[i]), tuple(int(v) for v in i), float(err[i]), float(bound[i])
-
-
-def describe(name, res) -> str:
-    ok, ratio, idx, err, bound = res
-    return f"{name}: worst element {idx}: |err| {err:.6e}, bound {bound:.6e}, err / bound {ratio:.4f}"
-
-
-# ------------------------------------------------------------------------------------------------------------------------------------
-# the operand dtypes and the single-rounding fma
-# ------------------------------------------------------------------------------------------------------------------------------------
-def bf16_bits(v) -> np.ndarray:
-    """fp32 -> the 16 bits of the nearest bf16, ties to even, by bit arithmetic (finite inputs)."""
-    b = np.ascontiguousarray(v, F32).view(np.uint32).astype(np.uint64)
-    return ((b + np.uint64(0x7FFF) + ((b >> np.uint64(16)) & np.uint64(1))) >> np.uint64(16)).astype(np.uint16)
-
-
-def to_bits(v, dt: str) -> np.ndarray:
-    """fp32 -> uint16 bit patterns of T (round to nearest even)."""
-    return np.ascontiguousarray(v, F32).astype(np.float16).view(np.uint16) if dt == "f16" else bf16_bits(v)
-
-
-def from_bits(bits, dt: str) -> np.ndarray:
-    """uint16 bit patterns of T -> fp32 (exact)."""
-    bits = np.ascontiguousarray(bits, np.uint16)
-    if dt == "f16":
-        return bits.view(np.float16).astype(F32)
-    return (bits.astype(np.uint32) << np.uint32(16)).view(F32)
-
-
-def round_T(v, dt: str) -> np.ndarray:
-    """fp32 -> fp32 holding the nearest value of T."""
-    v = np.asarray(v, F32)
-    return from_bits(to_bits(v, dt), dt).reshape(v.shape)
-
-
-def fma32(a, b, c) -> np.ndarray:
-    """fl32(a b + c) of fp32 arrays with one rounding (see the module docstring)."""
-    a, b, c = (np.asarray(v, F32).astype(F64) for v in (a, b, c))
-    p = a * b                                             # exact: 48 bits
-    s = np.atleast_1d(p + c)
-    p, c = np.broadcast_to(p, s.shape), np.broadcast_to(c, s.shape)
-    bb = s - p
-    res = (p - (s - bb)) + (c - bb)                       # TwoSum: p + c = s + res exactly
-    odd = (np.ascontiguousarray(s).view(np.int64) & 1) == 1
-    s = np.where((res != 0) & ~odd, np.nextafter(s, np.where(res > 0, np.inf, -np.inf)), s)      # round to odd
-    return s.astype(F32)
 
 
 def _fma(a64, b64, acc32):

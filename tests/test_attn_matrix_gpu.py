@@ -29,6 +29,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import attn_matrix as AM  # noqa: E402
+import matrix_common as MC  # noqa: E402
 from faceposegenerator_amd import _lib as L  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -40,15 +41,11 @@ FORMS = (2, 4, 8, 12)
 _SUMMARY = defaultdict(lambda: [0, 0.0, ""])       # (dtype, form) -> [launches, worst ratio, where]
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def _run(lib, case, recipe, dtype):
     """Launch one (case, recipe, dtype); returns (out [batch][heads][n_q][64], inputs on the device, packed buffers)."""
     inp = AM.make_inputs(case, recipe, dtype)
     pk = AM.pack(case, inp, dtype, DEV)
-    L.check(AM.launch(lib, case, pk, dtype, _stream()), f"idb_attention {case.name}")
+    L.check(AM.launch(lib, case, pk, dtype, MC.stream()), f"idb_attention {case.name}")
     torch.cuda.synchronize()
     out, touched = AM.unpack_out(case, pk, dtype)
     assert touched == 0, f"{case.name} {dtype} {recipe}: {touched} elements outside the output lost their canary"
@@ -94,7 +91,7 @@ def test_relaunch_is_bit_identical(lib, dtype):
         outs = []
         for _ in range(2):
             pk = AM.pack(case, inp, dtype, DEV)
-            L.check(AM.launch(lib, case, pk, dtype, _stream()), name)
+            L.check(AM.launch(lib, case, pk, dtype, MC.stream()), name)
             torch.cuda.synchronize()
             outs.append(pk.obuf.clone())
         assert torch.equal(outs[0], outs[1]), f"{name} {dtype}: two launches on the same inputs differ"
@@ -106,13 +103,13 @@ def test_graph_replay_equals_eager(lib, dtype):
     case = {c.name: c for c in AM.cases(lib)}["w8_nkv545"]
     inp = AM.make_inputs(case, "normal", dtype)
     pk = AM.pack(case, inp, dtype, DEV)
-    L.check(AM.launch(lib, case, pk, dtype, _stream()), "eager")
+    L.check(AM.launch(lib, case, pk, dtype, MC.stream()), "eager")
     torch.cuda.synchronize()
     eager = pk.obuf.clone()
     pk.obuf.fill_(AM.CANARY)
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        L.check(AM.launch(lib, case, pk, dtype, _stream()), "capture")
+        L.check(AM.launch(lib, case, pk, dtype, MC.stream()), "capture")
     pk.obuf.fill_(AM.CANARY)
     graph.replay()
     torch.cuda.synchronize()

@@ -13,14 +13,11 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import block_matrix as M  # noqa: E402
 import frblock_oracle as BO  # noqa: E402
+import matrix_common as MC  # noqa: E402
 
 F32, F64 = np.float32, np.float64
-_WORST = {}
+W = MC.Worst("block matrix, emulation")
 WHOLE = ("sc", "sh", "running_mean", "running_var", "gamma", "beta", "slope", "gc")       # single roundings: asked whole
-
-
-def _note(name, ratio):
-    _WORST[name] = max(_WORST.get(name, 0.0), ratio)
 
 
 # ---- plans ---------------------------------------------------------------------------------------------------------------------------
@@ -128,7 +125,7 @@ def test_conv_emulations_pass(n, case):
             emu = M.emulate_conv_dgrad(case) if op == "dgrad" else (M.emulate_conv_fwd if op == "fwd" else M.emulate_conv_wgrad)(case, mode)
             res = M.check(emu, ref, bound)
             assert res[0] and res[1] <= 0.5, M.describe(f"{op} {case} {mode}", res)
-            _note(f"conv {op}", res[1])
+            W.note(f"conv {op}", res[1])
             if op == "dgrad":
                 zero = np.broadcast_to(M.no_tap_mask(case)[None, :, :, None], emu.shape)
                 assert (emu.view(np.uint32)[zero] == 0).all() and (bound[zero] == 0).all() and (bound[~zero] > 0).all()
@@ -142,7 +139,7 @@ def test_bn_forward_emulation_passes(rows, ch):
     ok, res = M.judge_all(emu, ref, bound)
     for k, r in res.items():
         assert r[0] and r[1] <= (1.0 if k in WHOLE else 0.5), M.describe(f"bn forward {rows} x {ch} {k}", r)
-        _note(f"bn forward {k}", r[1])
+        W.note(f"bn forward {k}", r[1])
     assert emu["flags"] == (0, 0)
 
 
@@ -173,7 +170,7 @@ def test_bn_backward_emulation_passes(rows, ch):
         ok, res = M.judge_all(M.emulate_bn_backward(rows, ch, *form), ref, bound)
         for k, r in res.items():
             assert r[0], M.describe(f"bn backward {rows} x {ch} {form} {k}", r)          # every output is a single rounding: whole
-            _note(f"bn backward {k}", r[1])
+            W.note(f"bn backward {k}", r[1])
     if rows == 2:
         ref, _ = M.bn_backward_reference(rows, ch, True, False)
         assert ref["slope"][M.Y0_CH] == 0.0                                              # y == 0: d slope gets nothing
@@ -185,7 +182,7 @@ def test_affine_emulation_passes(rows, ch):
         ref, bound = M.affine_reference(rows, ch, *form)
         res = M.check(M.emulate_affine(rows, ch, *form), ref, bound)
         assert res[0], M.describe(f"affine {rows} x {ch} {form}", res)                    # single roundings: whole
-        _note("affine", res[1])
+        W.note("affine", res[1])
 
 
 def test_pack_emulation_is_the_copy():
@@ -196,25 +193,11 @@ def test_pack_emulation_is_the_copy():
 
 
 def test_summary():
-    for k in sorted(_WORST):
-        print(f"block matrix, emulation: {k}: worst err / bound {_WORST[k]:.4f}")
+    W.show()
 
 
 # ---- argument checks: every IDB_REQUIRE answers before any HIP call --------------------------------------------------------------------
-P16 = 1 << 20            # any non-null 16-byte-aligned address: none of these calls dereferences it
-EINVAL = -1
-OFF = P16 + 4            # 4-byte aligned only
-
-
-def _refused(lib, call, ok, variants, text):
-    """Every variant of the accepted argument set `ok` answers IDB_EINVAL with `text` in idb_last_error(), and launches nothing."""
-    before = lib.idb_launch_count()
-    for kw in variants:
-        assert set(kw) <= set(ok), kw
-        rc = call({**ok, **kw})
-        msg = lib.idb_last_error()
-        assert rc == EINVAL and msg and text.encode() in msg, (kw, rc, msg)
-    assert lib.idb_launch_count() == before
+P16, OFF = MC.P16, MC.OFF
 
 
 def _desc(a):
@@ -235,18 +218,18 @@ def test_conv_argument_checks(lib):
     dgr = lambda a: lib.idb_blk_conv_dgrad(C.byref(_desc(a)), a["g_out"], a["g_in"], None)                              # noqa: E731
     wgr = lambda a: lib.idb_blk_conv_wgrad(C.byref(_desc(a)), a["g_out"], a["d_weight"], a["ws"], a["ws_bytes"], None)  # noqa: E731
     for name, f in (("forward", fwd), ("dgrad", dgr), ("wgrad", wgr)):
-        _refused(lib, f, CONV_OK, DESC_BAD, f"idb_blk_conv_{name}: x, weight, affine and slope 16-byte aligned")
-        _refused(lib, f, CONV_OK, [dict(affine=None)], f"idb_blk_conv_{name}: a PReLU slope without")
-        _refused(lib, f, CONV_OK, [dict(x=None), dict(weight=None)], f"idb_blk_conv_{name}: null pointer")
-        _refused(lib, f, CONV_OK, [dict(cin=32), dict(cin=8), dict(cout=32), dict(h=129), dict(w=0), dict(b=1025), dict(ksize=2), dict(stride=3)],
+        MC.refused(lib, f, CONV_OK, DESC_BAD, f"idb_blk_conv_{name}: x, weight, affine and slope 16-byte aligned")
+        MC.refused(lib, f, CONV_OK, [dict(affine=None)], f"idb_blk_conv_{name}: a PReLU slope without")
+        MC.refused(lib, f, CONV_OK, [dict(x=None), dict(weight=None)], f"idb_blk_conv_{name}: null pointer")
+        MC.refused(lib, f, CONV_OK, [dict(cin=32), dict(cin=8), dict(cout=32), dict(h=129), dict(w=0), dict(b=1025), dict(ksize=2), dict(stride=3)],
                  f"idb_blk_conv_{name}: b in 1..1024")
-    _refused(lib, fwd, CONV_OK, [dict(out=OFF), dict(out=None)], "idb_blk_conv_forward: out null or not 16-byte aligned")
-    _refused(lib, dgr, CONV_OK, [dict(g_out=OFF), dict(g_in=OFF), dict(g_out=None), dict(g_in=None)], "idb_blk_conv_dgrad: g_out or g_in null")
-    _refused(lib, dgr, CONV_OK, [dict(cin=4, affine=None, slope=None)], "idb_blk_conv_dgrad: cin % 64 == 0 (the stem's image gradient is not built)")
-    _refused(lib, wgr, CONV_OK, [dict(g_out=OFF), dict(g_out=None), dict(d_weight=None)], "idb_blk_conv_wgrad: g_out or d_weight null")
+    MC.refused(lib, fwd, CONV_OK, [dict(out=OFF), dict(out=None)], "idb_blk_conv_forward: out null or not 16-byte aligned")
+    MC.refused(lib, dgr, CONV_OK, [dict(g_out=OFF), dict(g_in=OFF), dict(g_out=None), dict(g_in=None)], "idb_blk_conv_dgrad: g_out or g_in null")
+    MC.refused(lib, dgr, CONV_OK, [dict(cin=4, affine=None, slope=None)], "idb_blk_conv_dgrad: cin % 64 == 0 (the stem's image gradient is not built)")
+    MC.refused(lib, wgr, CONV_OK, [dict(g_out=OFF), dict(g_out=None), dict(d_weight=None)], "idb_blk_conv_wgrad: g_out or d_weight null")
     need = lib.idb_blk_conv_workspace_bytes(2, 3, 5, 64, 64, 3, 1, None, None)
     assert need == M.conv_plan((2, 3, 5, 64, 64, 3, 1))["bytes"]
-    _refused(lib, wgr, CONV_OK, [dict(ws=OFF), dict(ws=None), dict(ws_bytes=need - 1), dict(ws_bytes=0)], "idb_blk_conv_wgrad: workspace too small or unaligned")
+    MC.refused(lib, wgr, CONV_OK, [dict(ws=OFF), dict(ws=None), dict(ws_bytes=need - 1), dict(ws_bytes=0)], "idb_blk_conv_wgrad: workspace too small or unaligned")
 
 
 BN_OK = dict(x=P16, rows=257, ch=64, training=1, eps=1e-5, momentum=0.1, gamma=P16, beta=P16, rmean=P16, rvar=P16, stat=P16, affine=P16,
@@ -255,15 +238,15 @@ BN_OK = dict(x=P16, rows=257, ch=64, training=1, eps=1e-5, momentum=0.1, gamma=P
 
 def test_bn_forward_argument_checks(lib):
     f = lambda a: lib.idb_blk_bn_forward(*a.values())      # noqa: E731
-    _refused(lib, f, BN_OK, [dict(training=2), dict(training=-1)], "idb_blk_bn_forward: training must be 0 or 1")
-    _refused(lib, f, BN_OK, [dict(eps=-1e-9), dict(eps=1.5), dict(momentum=-0.1), dict(momentum=1.0 + 1e-9), dict(eps=float("nan")),
+    MC.refused(lib, f, BN_OK, [dict(training=2), dict(training=-1)], "idb_blk_bn_forward: training must be 0 or 1")
+    MC.refused(lib, f, BN_OK, [dict(eps=-1e-9), dict(eps=1.5), dict(momentum=-0.1), dict(momentum=1.0 + 1e-9), dict(eps=float("nan")),
                              dict(momentum=float("nan"))], "idb_blk_bn_forward: eps in [0, 1], momentum in [0, 1]")
-    _refused(lib, f, BN_OK, [dict(rows=1)], "idb_blk_bn_forward: one value per channel")
-    _refused(lib, f, BN_OK, [dict(rows=0), dict(ch=96), dict(ch=32), dict(ch=2112), dict(rows=1024 * 128 * 128 + 1)], "idb_blk_bn_forward: rows in 1..")
-    _refused(lib, f, BN_OK, [dict(affine=OFF), dict(stat=OFF)], "idb_blk_bn_forward: affine 16-byte, stat 8-byte aligned")
-    _refused(lib, f, BN_OK, [{k: None} for k in ("x", "gamma", "beta", "rmean", "rvar", "stat", "affine", "flags")], "idb_blk_bn_forward: null pointer")
+    MC.refused(lib, f, BN_OK, [dict(rows=1)], "idb_blk_bn_forward: one value per channel")
+    MC.refused(lib, f, BN_OK, [dict(rows=0), dict(ch=96), dict(ch=32), dict(ch=2112), dict(rows=1024 * 128 * 128 + 1)], "idb_blk_bn_forward: rows in 1..")
+    MC.refused(lib, f, BN_OK, [dict(affine=OFF), dict(stat=OFF)], "idb_blk_bn_forward: affine 16-byte, stat 8-byte aligned")
+    MC.refused(lib, f, BN_OK, [{k: None} for k in ("x", "gamma", "beta", "rmean", "rvar", "stat", "affine", "flags")], "idb_blk_bn_forward: null pointer")
     need = M.bn_plan(257, 64)["bytes"]
-    _refused(lib, f, BN_OK, [dict(ws=OFF), dict(ws=None), dict(ws_bytes=need - 1)], "idb_blk_bn_forward: workspace too small or unaligned")
+    MC.refused(lib, f, BN_OK, [dict(ws=OFF), dict(ws=None), dict(ws_bytes=need - 1)], "idb_blk_bn_forward: workspace too small or unaligned")
 
 
 BNB_OK = dict(c=P16, g=P16, rows=257, ch=64, stat=P16, affine=P16, gamma=P16, slope=P16, add=P16, d_gamma=P16, d_beta=P16, d_slope=P16, g_c=P16,
@@ -272,12 +255,12 @@ BNB_OK = dict(c=P16, g=P16, rows=257, ch=64, stat=P16, affine=P16, gamma=P16, sl
 
 def test_bn_backward_argument_checks(lib):
     f = lambda a: lib.idb_blk_bn_backward(*a.values())      # noqa: E731
-    _refused(lib, f, BNB_OK, [dict(rows=1), dict(rows=0), dict(ch=96)], "idb_blk_bn_backward: rows in 2..")
-    _refused(lib, f, BNB_OK, [dict(slope=None), dict(d_slope=None)], "idb_blk_bn_backward: slope and d_slope go together")
-    _refused(lib, f, BNB_OK, [dict(c=OFF), dict(g=OFF), dict(add=OFF), dict(g_c=OFF), dict(stat=OFF)], "idb_blk_bn_backward: c, g, add and g_c 16-byte")
-    _refused(lib, f, BNB_OK, [{k: None} for k in ("c", "g", "stat", "affine", "gamma", "d_gamma", "d_beta", "g_c")], "idb_blk_bn_backward: null pointer")
+    MC.refused(lib, f, BNB_OK, [dict(rows=1), dict(rows=0), dict(ch=96)], "idb_blk_bn_backward: rows in 2..")
+    MC.refused(lib, f, BNB_OK, [dict(slope=None), dict(d_slope=None)], "idb_blk_bn_backward: slope and d_slope go together")
+    MC.refused(lib, f, BNB_OK, [dict(c=OFF), dict(g=OFF), dict(add=OFF), dict(g_c=OFF), dict(stat=OFF)], "idb_blk_bn_backward: c, g, add and g_c 16-byte")
+    MC.refused(lib, f, BNB_OK, [{k: None} for k in ("c", "g", "stat", "affine", "gamma", "d_gamma", "d_beta", "g_c")], "idb_blk_bn_backward: null pointer")
     need = M.bn_plan(257, 64)["bytes"]
-    _refused(lib, f, BNB_OK, [dict(ws=OFF), dict(ws=None), dict(ws_bytes=need - 1)], "idb_blk_bn_backward: workspace too small or unaligned")
+    MC.refused(lib, f, BNB_OK, [dict(ws=OFF), dict(ws=None), dict(ws_bytes=need - 1)], "idb_blk_bn_backward: workspace too small or unaligned")
 
 
 AFF_OK = dict(c=P16, affine=P16, slope=P16, identity=P16, id_affine=P16, rows=3, ch=64, out=P16, stream=None)
@@ -285,19 +268,19 @@ AFF_OK = dict(c=P16, affine=P16, slope=P16, identity=P16, id_affine=P16, rows=3,
 
 def test_affine_pack_and_sgd_argument_checks(lib):
     f = lambda a: lib.idb_blk_affine(*a.values())      # noqa: E731
-    _refused(lib, f, AFF_OK, [{k: OFF} for k in ("c", "affine", "slope", "identity", "id_affine", "out")], "idb_blk_affine: every pointer 16-byte aligned")
-    _refused(lib, f, AFF_OK, [dict(identity=None)], "idb_blk_affine: an identity affine pair without the identity")
-    _refused(lib, f, AFF_OK, [dict(c=None), dict(affine=None), dict(out=None)], "idb_blk_affine: null pointer")
-    _refused(lib, f, AFF_OK, [dict(rows=0), dict(ch=4), dict(ch=100)], "idb_blk_affine: rows in 1..")
+    MC.refused(lib, f, AFF_OK, [{k: OFF} for k in ("c", "affine", "slope", "identity", "id_affine", "out")], "idb_blk_affine: every pointer 16-byte aligned")
+    MC.refused(lib, f, AFF_OK, [dict(identity=None)], "idb_blk_affine: an identity affine pair without the identity")
+    MC.refused(lib, f, AFF_OK, [dict(c=None), dict(affine=None), dict(out=None)], "idb_blk_affine: null pointer")
+    MC.refused(lib, f, AFF_OK, [dict(rows=0), dict(ch=4), dict(ch=100)], "idb_blk_affine: rows in 1..")
     pk = dict(images=P16, b=2, h=15, w=17, out=P16, stream=None)
     f = lambda a: lib.idb_blk_pack_images(*a.values())      # noqa: E731
-    _refused(lib, f, pk, [dict(h=129), dict(w=129), dict(h=0), dict(b=0), dict(b=1025)], "idb_blk_pack_images: b in 1..1024")
-    _refused(lib, f, pk, [dict(out=OFF), dict(out=None), dict(images=None)], "idb_blk_pack_images: null pointer, or out not 16-byte aligned")
+    MC.refused(lib, f, pk, [dict(h=129), dict(w=129), dict(h=0), dict(b=0), dict(b=1025)], "idb_blk_pack_images: b in 1..1024")
+    MC.refused(lib, f, pk, [dict(out=OFF), dict(out=None), dict(images=None)], "idb_blk_pack_images: null pointer, or out not 16-byte aligned")
     sg = dict(count=3, w=P16, g=P16, buf=P16, n=P16, lr=0.1, momentum=0.9, wd=5e-4, max_norm=5.0, first=1, total=P16, ws=P16, ws_bytes=1 << 30,
               stream=None)
     f = lambda a: lib.idb_sgd_clip_step_table(*a.values())      # noqa: E731
-    _refused(lib, f, sg, [dict(count=0), dict(count=1025), dict(count=-1)], "idb_sgd_clip_step_table: 1..1024 tensors")
-    _refused(lib, f, sg, [{k: OFF} for k in ("w", "g", "buf", "n", "total")], "idb_sgd_clip_step_table: total_norm and the tables 8-byte aligned")
-    _refused(lib, f, sg, [dict(ws_bytes=8 * 3 * 1024 - 1), dict(ws=OFF)], "idb_sgd_clip_step_table: workspace too small or unaligned")
+    MC.refused(lib, f, sg, [dict(count=0), dict(count=1025), dict(count=-1)], "idb_sgd_clip_step_table: 1..1024 tensors")
+    MC.refused(lib, f, sg, [{k: OFF} for k in ("w", "g", "buf", "n", "total")], "idb_sgd_clip_step_table: total_norm and the tables 8-byte aligned")
+    MC.refused(lib, f, sg, [dict(ws_bytes=8 * 3 * 1024 - 1), dict(ws=OFF)], "idb_sgd_clip_step_table: workspace too small or unaligned")
     assert lib.idb_sgd_clip_table_workspace_bytes(0) == 0 and lib.idb_sgd_clip_table_workspace_bytes(1025) == 0
     assert lib.idb_sgd_clip_table_workspace_bytes(1) == 8 * 1024 and lib.idb_sgd_clip_table_workspace_bytes(1024) == 8 * 1024 * 1024

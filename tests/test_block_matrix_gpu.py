@@ -30,73 +30,20 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import block_matrix as M  # noqa: E402
 import frtail_oracle as TO  # noqa: E402
+import matrix_common as MC  # noqa: E402
 from faceposegenerator_amd import _lib as L  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-G = M.GUARD
 F32, F64 = np.float32, np.float64
-_WORST = {}
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _dev(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, F32)).to(DEV)
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _judge(key, what, got, ref, bound):
-    res = M.check(np.asarray(got, F64).reshape(np.shape(ref)), ref, bound)
-    print(M.describe(what, res))
-    assert res[0], M.describe(what, res)
-    if key not in _WORST or res[1] > _WORST[key][0]:
-        _WORST[key] = (res[1], what)
-
-
-class _Buf:
-    """n 32-bit words between guards of the NaN pattern; pre-filled with the pattern, or with `init` (fp32 or int32 values)."""
-
-    def __init__(self, n, init=None):
-        self.n = n
-        self.buf = torch.full((n + 2 * G,), M.NAN32, dtype=torch.int32, device=DEV)
-        if init is not None:
-            self.buf[G:G + n] = torch.from_numpy(np.ascontiguousarray(init).view(np.int32).reshape(-1)).to(DEV)
-        self.ptr = self.buf.data_ptr() + 4 * G
-        assert self.ptr % 16 == 0
-
-    def raw(self, what):
-        host = self.buf.cpu().numpy()
-        assert (host[:G] == M.NAN32).all() and (host[G + self.n:] == M.NAN32).all(), f"{what}: guard words overwritten"
-        return host[G:G + self.n]
-
-    def f32(self, what):
-        return self.raw(what).view(F32)
-
-    def f64(self, what):
-        return self.raw(what).view(F64)
-
-    def untouched(self, what):
-        return bool((self.raw(what) == M.NAN32).all())
-
-
-def _same(what, a, b):
-    a, b = np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32)
-    diff = np.argwhere(a.reshape(-1) != b.reshape(-1))
-    assert diff.size == 0, f"{what}: {diff.shape[0]} elements differ, the first at {int(diff[0, 0])}: {int(a.reshape(-1)[diff[0, 0]]):#010x} against {int(b.reshape(-1)[diff[0, 0]]):#010x}"
+W = MC.Worst("block matrix")
 
 
 # ---- convolutions --------------------------------------------------------------------------------------------------------------------
 def _desc(case, x_ptr, aff, sl, w):
     d = L.BlkConvDesc()
     d.b, d.h, d.w, d.cin, d.cout, d.ksize, d.stride = case
-    d.x, d.affine, d.slope, d.weight = x_ptr, _p(aff), _p(sl), _p(w)
+    d.x, d.affine, d.slope, d.weight = x_ptr, MC.ptr(aff), MC.ptr(sl), MC.ptr(w)
     return d
 
 
@@ -104,16 +51,16 @@ class _Conv:
     def __init__(self, case, mode):
         self.case, self.mode, self.g = case, mode, M.conv_geo(case)
         x, w, go, aff, sl = M.conv_operands(case, mode)
-        self.x, self.w, self.go, self.aff, self.sl = _dev(x), _dev(w), _dev(go), _dev(aff), _dev(sl)
+        self.x, self.w, self.go, self.aff, self.sl = (MC.dev(v, F32) for v in (x, w, go, aff, sl))
         self.desc = _desc(case, self.x.data_ptr(), self.aff, self.sl, self.w)
         self.what = f"{case} {mode}"
 
     def preactivated(self, lib):
         """The descriptor of the same conv on idb_blk_affine(x, affine, slope) with no affine pair."""
         g = self.g
-        self.pre = _Buf(self.x.numel())
-        L.check(lib.idb_blk_affine(self.x.data_ptr(), self.aff.data_ptr(), _p(self.sl), None, None, g["B"] * g["H"] * g["W"], g["cin"], self.pre.ptr,
-                                   _stream()), "idb_blk_affine " + self.what)
+        self.pre = MC.Guarded(self.x.numel())
+        L.check(lib.idb_blk_affine(self.x.data_ptr(), self.aff.data_ptr(), MC.ptr(self.sl), None, None, g["B"] * g["H"] * g["W"], g["cin"], self.pre.ptr,
+                                   MC.stream()), "idb_blk_affine " + self.what)
         return _desc(self.case, self.pre.ptr, None, None, self.w)
 
 
@@ -124,20 +71,20 @@ CONV_PARAMS = [(c, m) for c in M.CONV_CASES for m in M.conv_modes(c)]
 def test_conv_forward(lib, case, mode):
     cv = _Conv(case, mode)
     what, n = "idb_blk_conv_forward " + cv.what, cv.g["Mo"] * cv.g["cout"]
-    out, again = _Buf(n), _Buf(n)
+    out, again = MC.Guarded(n), MC.Guarded(n)
     for o in (out, again):
-        L.check(lib.idb_blk_conv_forward(C.byref(cv.desc), o.ptr, _stream()), what)
+        L.check(lib.idb_blk_conv_forward(C.byref(cv.desc), o.ptr, MC.stream()), what)
     pre = None
     if cv.aff is not None:
-        pre = _Buf(n)
-        L.check(lib.idb_blk_conv_forward(C.byref(cv.preactivated(lib)), pre.ptr, _stream()), what + " (pre-activated)")
+        pre = MC.Guarded(n)
+        L.check(lib.idb_blk_conv_forward(C.byref(cv.preactivated(lib)), pre.ptr, MC.stream()), what + " (pre-activated)")
     torch.cuda.synchronize()
     ref, bound = M.conv_reference(case, mode, "fwd")
     got = out.f32(what)
-    _judge("conv forward", what, got, ref, bound)
-    _same(what + ": a repeat", got, again.f32(what))
+    W.judge("conv forward", what, got.reshape(ref.shape), ref, bound)
+    MC.same_bits(what + ": a repeat", got, again.f32(what))
     if pre is not None:
-        _same(what + ": the load-path activation against idb_blk_affine's", got, pre.f32(what))
+        MC.same_bits(what + ": the load-path activation against idb_blk_affine's", got, pre.f32(what))
 
 
 @pytest.mark.parametrize("case", M.CONV_CASES, ids=str)
@@ -148,8 +95,8 @@ def test_conv_dgrad(lib, case):
     for mode in M.conv_modes(case) + M.conv_modes(case)[:1]:          # every mode, and a repeat of the first
         cv = _Conv(case, mode)
         what = "idb_blk_conv_dgrad " + cv.what
-        gi = _Buf(n)
-        rc = lib.idb_blk_conv_dgrad(C.byref(cv.desc), cv.go.data_ptr(), gi.ptr, _stream())
+        gi = MC.Guarded(n)
+        rc = lib.idb_blk_conv_dgrad(C.byref(cv.desc), cv.go.data_ptr(), gi.ptr, MC.stream())
         torch.cuda.synchronize()
         if g["cin"] == 4:
             assert rc != 0 and b"cin % 64 == 0" in lib.idb_last_error() and gi.untouched(what), what
@@ -159,11 +106,11 @@ def test_conv_dgrad(lib, case):
     if g["cin"] == 4:
         return
     ref, bound = M.conv_reference(case, "plain", "dgrad")
-    _judge("conv dgrad", what, outs[0], ref, bound)
+    W.judge("conv dgrad", what, outs[0].reshape(ref.shape), ref, bound)
     zero = np.broadcast_to(M.no_tap_mask(case)[None, :, :, None], ref.shape).reshape(-1)
     assert (outs[0].view(np.uint32)[zero] == 0).all(), f"{what}: a pixel no tap reaches is not an exact +0"
     for o in outs[1:]:
-        _same(what + ": a repeat, or another affine pair in the descriptor", outs[0], o)
+        MC.same_bits(what + ": a repeat, or another affine pair in the descriptor", outs[0], o)
 
 
 @pytest.mark.parametrize("case,mode", CONV_PARAMS, ids=lambda v: str(v))
@@ -174,17 +121,17 @@ def test_conv_wgrad(lib, case, mode):
     need = lib.idb_blk_conv_workspace_bytes(*case, None, None)
     assert need == p["bytes"] and need % 4 == 0
     descs = [cv.desc, cv.desc] + ([cv.preactivated(lib)] if cv.aff is not None else [])
-    outs, works = [_Buf(n) for _ in descs], [_Buf(need // 4) for _ in descs]
+    outs, works = [MC.Guarded(n) for _ in descs], [MC.Guarded(need // 4) for _ in descs]
     for d, o, ws in zip(descs, outs, works):
-        L.check(lib.idb_blk_conv_wgrad(C.byref(d), cv.go.data_ptr(), o.ptr, ws.ptr, need, _stream()), what)
+        L.check(lib.idb_blk_conv_wgrad(C.byref(d), cv.go.data_ptr(), o.ptr, ws.ptr, need, MC.stream()), what)
     torch.cuda.synchronize()
     ref, bound = M.conv_reference(case, mode, "wgrad")
     got = outs[0].f32(what)
-    _judge("conv wgrad", what, got, ref, bound)
+    W.judge("conv wgrad", what, got.reshape(ref.shape), ref, bound)
     assert np.isfinite(works[0].f32(what + " workspace")[:p["slices"] * n]).all(), f"{what}: an element of a slice's partial was not written"
-    _same(what + ": a repeat", got, outs[1].f32(what))
+    MC.same_bits(what + ": a repeat", got, outs[1].f32(what))
     if len(descs) == 3:
-        _same(what + ": the load-path activation against idb_blk_affine's", got, outs[2].f32(what))
+        MC.same_bits(what + ": the load-path activation against idb_blk_affine's", got, outs[2].f32(what))
         works[2].raw(what + " workspace")
 
 
@@ -193,12 +140,12 @@ def _bn_forward(lib, x, prm, what, training=1, eps=M.EPS, momentum=M.MOMENTUM):
     rows, ch = x.shape
     need = lib.idb_blk_bn_workspace_bytes(rows, ch, None)
     assert need == M.bn_plan(rows, ch)["bytes"]
-    dx = x if torch.is_tensor(x) else _dev(x)
-    gam, beta = _dev(prm["bn.weight"]), _dev(prm["bn.bias"])
-    rm, rv = _Buf(ch, prm["bn.running_mean"].astype(F32)), _Buf(ch, prm["bn.running_var"].astype(F32))
-    stat, aff, flags, ws = _Buf(4 * ch), _Buf(2 * ch), _Buf(2, np.zeros(2, np.int32)), _Buf(need // 4)
+    dx = x if torch.is_tensor(x) else MC.dev(x, F32)
+    gam, beta = MC.dev(prm["bn.weight"], F32), MC.dev(prm["bn.bias"], F32)
+    rm, rv = MC.Guarded(ch, init=prm["bn.running_mean"].astype(F32)), MC.Guarded(ch, init=prm["bn.running_var"].astype(F32))
+    stat, aff, flags, ws = MC.Guarded(4 * ch), MC.Guarded(2 * ch), MC.Guarded(2, init=np.zeros(2, np.int32)), MC.Guarded(need // 4)
     L.check(lib.idb_blk_bn_forward(dx.data_ptr(), rows, ch, training, eps, momentum, gam.data_ptr(), beta.data_ptr(), rm.ptr, rv.ptr, stat.ptr, aff.ptr,
-                                   flags.ptr, ws.ptr, need, _stream()), what)
+                                   flags.ptr, ws.ptr, need, MC.stream()), what)
     torch.cuda.synchronize()
     ws.raw(what + " workspace")
     st, af = stat.f64(what).reshape(2, ch), aff.f32(what).reshape(2, ch)
@@ -208,21 +155,21 @@ def _bn_forward(lib, x, prm, what, training=1, eps=M.EPS, momentum=M.MOMENTUM):
 def _judge_bn(what, got, ref, bound, keep=None):
     for k in ref:
         sel = slice(None) if keep is None else keep
-        _judge(f"bn forward {k}", f"{what} {k}", got[k][sel], ref[k][sel], bound[k][sel])
+        W.judge(f"bn forward {k}", f"{what} {k}", got[k][sel].reshape(ref[k][sel].shape), ref[k][sel], bound[k][sel])
 
 
 @pytest.mark.parametrize("rows,ch", M.bn_cases())
 def test_bn_forward(lib, rows, ch):
     what = f"idb_blk_bn_forward {rows} x {ch}"
     x, prm = M.bn_inputs(rows, ch)
-    dx = _dev(x)
+    dx = MC.dev(x, F32)
     got, flags = _bn_forward(lib, dx, prm, what)
     again, _ = _bn_forward(lib, dx, prm, what)
     ref, bound = M.bn_forward_reference(x, prm)
     _judge_bn(what, got, ref, bound)
     assert flags == (0, 0), (what, flags)
     for k in got:
-        _same(f"{what} {k}: a repeat", got[k], again[k])
+        MC.same_bits(f"{what} {k}: a repeat", got[k], again[k])
 
 
 def test_bn_forward_planted_channels_eval_and_momentum(lib):
@@ -245,8 +192,8 @@ def test_bn_forward_planted_channels_eval_and_momentum(lib):
     ref, bound = M.bn_forward_reference(x[:1], prm, training=False)
     _judge_bn(what, got, ref, bound)
     assert flags == (0, 0)
-    _same(what + ": the running mean is left as it was", got["running_mean"], prm["bn.running_mean"].astype(F32))
-    _same(what + ": the running variance is left as it was", got["running_var"], prm["bn.running_var"].astype(F32))
+    MC.same_bits(what + ": the running mean is left as it was", got["running_mean"], prm["bn.running_mean"].astype(F32))
+    MC.same_bits(what + ": the running variance is left as it was", got["running_var"], prm["bn.running_var"].astype(F32))
     for mom in (0.0, 1.0):
         what = f"idb_blk_bn_forward, momentum {mom}"
         got, flags = _bn_forward(lib, x, prm, what, momentum=mom)
@@ -254,7 +201,7 @@ def test_bn_forward_planted_channels_eval_and_momentum(lib):
         _judge_bn(what, got, ref, bound)
         assert flags == (0, 0)
         if mom == 0.0:
-            _same(what + ": the running mean is left as it was", got["running_mean"], prm["bn.running_mean"].astype(F32))
+            MC.same_bits(what + ": the running mean is left as it was", got["running_mean"], prm["bn.running_mean"].astype(F32))
 
 
 # ---- BatchNorm backward and the affine kernel ------------------------------------------------------------------------------------------
@@ -262,17 +209,17 @@ class _Bnb:
     def __init__(self, rows, ch):
         i = M.bnb_inputs(rows, ch)
         self.rows, self.ch = rows, ch
-        self.c, self.g, self.add, self.gamma, self.slope = (_dev(i[k]) for k in ("c", "g", "add", "gamma", "slope"))
-        self.aff, self.id_aff = _dev(i["affine"]), _dev(i["id_affine"])
-        self.stat = torch.from_numpy(np.array(i["stat"], F64)).to(DEV)
+        self.c, self.g, self.add, self.gamma, self.slope = (MC.dev(i[k], F32) for k in ("c", "g", "add", "gamma", "slope"))
+        self.aff, self.id_aff = MC.dev(i["affine"], F32), MC.dev(i["id_affine"], F32)
+        self.stat = torch.from_numpy(np.array(i["stat"], F64)).to(MC.DEV)
 
     def backward(self, lib, with_slope, with_add, what):
         rows, ch = self.rows, self.ch
         need = lib.idb_blk_bn_workspace_bytes(rows, ch, None)
-        dgam, dbeta, dsl, gc, ws = _Buf(ch), _Buf(ch), (_Buf(ch) if with_slope else None), _Buf(rows * ch), _Buf(need // 4)
+        dgam, dbeta, dsl, gc, ws = MC.Guarded(ch), MC.Guarded(ch), (MC.Guarded(ch) if with_slope else None), MC.Guarded(rows * ch), MC.Guarded(need // 4)
         L.check(lib.idb_blk_bn_backward(self.c.data_ptr(), self.g.data_ptr(), rows, ch, self.stat.data_ptr(), self.aff.data_ptr(), self.gamma.data_ptr(),
-                                        _p(self.slope) if with_slope else None, _p(self.add) if with_add else None, dgam.ptr, dbeta.ptr,
-                                        dsl.ptr if with_slope else None, gc.ptr, ws.ptr, need, _stream()), what)
+                                        MC.ptr(self.slope) if with_slope else None, MC.ptr(self.add) if with_add else None, dgam.ptr, dbeta.ptr,
+                                        dsl.ptr if with_slope else None, gc.ptr, ws.ptr, need, MC.stream()), what)
         torch.cuda.synchronize()
         ws.raw(what + " workspace")
         out = dict(gc=gc.f32(what), gamma=dgam.f32(what), beta=dbeta.f32(what))
@@ -281,10 +228,10 @@ class _Bnb:
         return out
 
     def affine(self, lib, with_slope, identity, what):
-        out = _Buf(self.rows * self.ch)
-        L.check(lib.idb_blk_affine(self.c.data_ptr(), self.aff.data_ptr(), _p(self.slope) if with_slope else None,
+        out = MC.Guarded(self.rows * self.ch)
+        L.check(lib.idb_blk_affine(self.c.data_ptr(), self.aff.data_ptr(), MC.ptr(self.slope) if with_slope else None,
                                    None if identity == "none" else self.add.data_ptr(), self.id_aff.data_ptr() if identity == "affine" else None,
-                                   self.rows, self.ch, out.ptr, _stream()), what)
+                                   self.rows, self.ch, out.ptr, MC.stream()), what)
         torch.cuda.synchronize()
         return out.f32(what)
 
@@ -297,11 +244,11 @@ def test_bn_backward(lib, rows, ch):
         got = dev.backward(lib, *form, what)
         ref, bound = M.bn_backward_reference(rows, ch, *form)
         for k in ref:
-            _judge(f"bn backward {k}", f"{what} {k}", got[k], ref[k], bound[k])
+            W.judge(f"bn backward {k}", f"{what} {k}", got[k].reshape(ref[k].shape), ref[k], bound[k])
         if form == M.BNB_FORMS[3]:
             again = dev.backward(lib, *form, what)
             for k in got:
-                _same(f"{what} {k}: a repeat", got[k], again[k])
+                MC.same_bits(f"{what} {k}: a repeat", got[k], again[k])
 
 
 @pytest.mark.parametrize("rows,ch", M.bn_cases())
@@ -311,9 +258,9 @@ def test_affine(lib, rows, ch):
         what = f"idb_blk_affine {rows} x {ch} slope {form[0]} identity {form[1]}"
         got = dev.affine(lib, *form, what)
         ref, bound = M.affine_reference(rows, ch, *form)
-        _judge("affine", what, got, ref, bound)
+        W.judge("affine", what, got.reshape(ref.shape), ref, bound)
         if form == M.AFFINE_FORMS[5]:
-            _same(what + ": a repeat", got, dev.affine(lib, *form, what))
+            MC.same_bits(what + ": a repeat", got, dev.affine(lib, *form, what))
 
 
 # ---- pack and the table SGD ------------------------------------------------------------------------------------------------------------
@@ -321,37 +268,37 @@ def test_affine(lib, rows, ch):
 def test_pack_images(lib, shape):
     what = f"idb_blk_pack_images {shape}"
     b, h, w = shape
-    img = _dev(M.pack_input(shape))
-    out, again = _Buf(b * h * w * 4), _Buf(b * h * w * 4)
+    img = MC.dev(M.pack_input(shape), F32)
+    out, again = MC.Guarded(b * h * w * 4), MC.Guarded(b * h * w * 4)
     for o in (out, again):
-        L.check(lib.idb_blk_pack_images(img.data_ptr(), b, h, w, o.ptr, _stream()), what)
+        L.check(lib.idb_blk_pack_images(img.data_ptr(), b, h, w, o.ptr, MC.stream()), what)
     torch.cuda.synchronize()
-    _same(what, out.f32(what), M.pack_reference(shape))
-    _same(what + ": a repeat", out.f32(what), again.f32(what))
+    MC.same_bits(what, out.f32(what), M.pack_reference(shape))
+    MC.same_bits(what + ": a repeat", out.f32(what), again.f32(what))
 
 
 @pytest.mark.parametrize("count", M.SGD_COUNTS)
 def test_sgd_table(lib, count):
     sizes = M.sgd_sizes(count)
     tensors = lambda salt: [((TO._h(np.arange(n) + 5 * i + salt, 201) - 100) / 100.0).astype(F32) for i, n in enumerate(sizes)]      # noqa: E731
-    table = lambda ts: torch.tensor([t.ptr for t in ts], dtype=torch.int64).to(DEV)                                              # noqa: E731
+    table = lambda ts: torch.tensor([t.ptr for t in ts], dtype=torch.int64).to(MC.DEV)                                              # noqa: E731
     w0 = tensors(2)
-    ws, bufs = [_Buf(n, w) for n, w in zip(sizes, w0)], [_Buf(n) for n in sizes]
+    ws, bufs = [MC.Guarded(n, init=w) for n, w in zip(sizes, w0)], [MC.Guarded(n) for n in sizes]
     ref_w, ref_b, total = [w.astype(F64) for w in w0], None, sum(sizes)
     eb, ew = [np.zeros(n) for n in sizes], [np.zeros(n) for n in sizes]
     lr, mom, wd = 0.1, 0.9, 5e-4
     need = lib.idb_sgd_clip_table_workspace_bytes(count)
-    work, norm = _Buf(need // 4), _Buf(2)
-    numel = torch.tensor(sizes, dtype=torch.int64).to(DEV)
+    work, norm = MC.Guarded(need // 4), MC.Guarded(2)
+    numel = torch.tensor(sizes, dtype=torch.int64).to(MC.DEV)
     tw, tb = table(ws), table(bufs)
     for step, scale in enumerate((0.5, 0.01)):
         what = f"idb_sgd_clip_step_table, {count} tensors, step {step + 1}"
         g0 = [g * F32(scale) for g in tensors(11 + step)]
-        gs = [_dev(g) for g in g0]
-        tg = torch.tensor([g.data_ptr() for g in gs], dtype=torch.int64).to(DEV)
+        gs = [MC.dev(g, F32) for g in g0]
+        tg = torch.tensor([g.data_ptr() for g in gs], dtype=torch.int64).to(MC.DEV)
         ref_w, ref_b, ref_norm = TO.sgd_step(ref_w, [g.astype(F64) for g in g0], ref_b, lr, mom, wd, 5.0)
         L.check(lib.idb_sgd_clip_step_table(count, tw.data_ptr(), tg.data_ptr(), tb.data_ptr(), numel.data_ptr(), lr, mom, wd, 5.0, int(step == 0),
-                                            norm.ptr, work.ptr, need, _stream()), what)
+                                            norm.ptr, work.ptr, need, MC.stream()), what)
         torch.cuda.synchronize()
         work.raw(what + " workspace")
         assert abs(float(norm.f64(what)[0]) - ref_norm) <= (total + 8) * TO.U64 * ref_norm, what
@@ -360,8 +307,8 @@ def test_sgd_table(lib, count):
         gb = np.concatenate([b.f32(what) for b in bufs])
         for i in range(count):
             eb[i], ew[i] = TO.sgd_bound(ref_w[i], ref_b[i], eb[i], ew[i], lr, mom, wd, coef * np.abs(g0[i].astype(F64)), total)
-        _judge("table sgd weight", what + " weight", gw, np.concatenate(ref_w), np.concatenate(ew))
-        _judge("table sgd momentum", what + " momentum", gb, np.concatenate(ref_b), np.concatenate(eb))
+        W.judge("table sgd weight", what + " weight", gw, np.concatenate(ref_w), np.concatenate(ew))
+        W.judge("table sgd momentum", what + " momentum", gb, np.concatenate(ref_b), np.concatenate(eb))
 
 
 # ---- refusals leave guards and outputs as they were ------------------------------------------------------------------------------------
@@ -369,28 +316,28 @@ def test_refusals_leave_outputs_untouched(lib):
     case = M.CONV_CASES[4]
     cv = _Conv(case, "prelu")
     g, n = cv.g, cv.g["Mo"] * cv.g["cout"]
-    out, dw = _Buf(n), _Buf(g["cout"] * g["K"])
+    out, dw = MC.Guarded(n), MC.Guarded(g["cout"] * g["K"])
     need = lib.idb_blk_conv_workspace_bytes(*case, None, None)
-    ws = _Buf(need // 4)
+    ws = MC.Guarded(need // 4)
     before = lib.idb_launch_count()
     d = _desc(case, cv.x.data_ptr(), None, cv.sl, cv.w)                                       # a slope without the affine pair
-    assert lib.idb_blk_conv_forward(C.byref(d), out.ptr, _stream()) != 0 and b"a PReLU slope without" in lib.idb_last_error()
+    assert lib.idb_blk_conv_forward(C.byref(d), out.ptr, MC.stream()) != 0 and b"a PReLU slope without" in lib.idb_last_error()
     d = _desc(case, cv.x.data_ptr() + 4, cv.aff, cv.sl, cv.w)                                   # x misaligned
-    assert lib.idb_blk_conv_forward(C.byref(d), out.ptr, _stream()) != 0 and b"16-byte aligned" in lib.idb_last_error()
-    assert lib.idb_blk_conv_wgrad(C.byref(cv.desc), cv.go.data_ptr(), dw.ptr, ws.ptr, need - 1, _stream()) != 0      # one byte short
+    assert lib.idb_blk_conv_forward(C.byref(d), out.ptr, MC.stream()) != 0 and b"16-byte aligned" in lib.idb_last_error()
+    assert lib.idb_blk_conv_wgrad(C.byref(cv.desc), cv.go.data_ptr(), dw.ptr, ws.ptr, need - 1, MC.stream()) != 0      # one byte short
     assert b"workspace too small" in lib.idb_last_error()
     dev = _Bnb(2, 64)
-    gc, dgam, dbeta, dsl, bws = _Buf(2 * 64), _Buf(64), _Buf(64), _Buf(64), _Buf(lib.idb_blk_bn_workspace_bytes(2, 64, None) // 4)
+    gc, dgam, dbeta, dsl, bws = MC.Guarded(2 * 64), MC.Guarded(64), MC.Guarded(64), MC.Guarded(64), MC.Guarded(lib.idb_blk_bn_workspace_bytes(2, 64, None) // 4)
     args = lambda rows, sl, dsl_: (dev.c.data_ptr(), dev.g.data_ptr(), rows, 64, dev.stat.data_ptr(), dev.aff.data_ptr(), dev.gamma.data_ptr(), sl, None,      # noqa: E731
-                                   dgam.ptr, dbeta.ptr, dsl_, gc.ptr, bws.ptr, 4 * bws.n, _stream())
+                                   dgam.ptr, dbeta.ptr, dsl_, gc.ptr, bws.ptr, 4 * bws.n, MC.stream())
     assert lib.idb_blk_bn_backward(*args(1, dev.slope.data_ptr(), dsl.ptr)) != 0 and b"rows in 2.." in lib.idb_last_error()
     assert lib.idb_blk_bn_backward(*args(2, dev.slope.data_ptr(), None)) != 0 and b"go together" in lib.idb_last_error()
     assert lib.idb_blk_bn_backward(*args(2, None, dsl.ptr)) != 0 and b"go together" in lib.idb_last_error()
-    aout = _Buf(2 * 64)
-    assert lib.idb_blk_affine(dev.c.data_ptr(), dev.aff.data_ptr(), None, None, dev.id_aff.data_ptr(), 2, 64, aout.ptr, _stream()) != 0
+    aout = MC.Guarded(2 * 64)
+    assert lib.idb_blk_affine(dev.c.data_ptr(), dev.aff.data_ptr(), None, None, dev.id_aff.data_ptr(), 2, 64, aout.ptr, MC.stream()) != 0
     assert b"without the identity" in lib.idb_last_error()
-    img, pout = _dev(np.zeros((1, 3, 129, 1))), _Buf(129 * 4)
-    assert lib.idb_blk_pack_images(img.data_ptr(), 1, 129, 1, pout.ptr, _stream()) != 0 and b"h and w in 1..128" in lib.idb_last_error()
+    img, pout = MC.dev(np.zeros((1, 3, 129, 1)), F32), MC.Guarded(129 * 4)
+    assert lib.idb_blk_pack_images(img.data_ptr(), 1, 129, 1, pout.ptr, MC.stream()) != 0 and b"h and w in 1..128" in lib.idb_last_error()
     torch.cuda.synchronize()
     assert lib.idb_launch_count() == before
     for name, b in (("out", out), ("d_weight", dw), ("wgrad workspace", ws), ("g_c", gc), ("d_gamma", dgam), ("d_beta", dbeta), ("d_slope", dsl),
@@ -399,5 +346,4 @@ def test_refusals_leave_outputs_untouched(lib):
 
 
 def test_summary():
-    for k in sorted(_WORST):
-        print(f"block matrix: {k}: worst err / bound {_WORST[k][0]:.4f} ({_WORST[k][1]})")
+    W.show()

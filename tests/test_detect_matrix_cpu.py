@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import detect_matrix as D  # noqa: E402
+import matrix_common as MC  # noqa: E402
 
 AREA = D.area_cases()
 CONV = D.conv_cases()
@@ -119,7 +120,7 @@ def test_pool_reference_is_torch_max_pool2d():
         xp[:, :h, :w] = x
         want = F.max_pool2d(torch.from_numpy(xp)[None], k, s, ceil_mode=True)[0].numpy()[:, :ref.shape[1], :ref.shape[2]]
         assert ref.shape == (x.shape[0], D.pool_outputs(h, k, s), D.pool_outputs(w, k, s))
-        assert D.bit_equal(ref, want.astype(np.float32))[0], (h, w, k, s)
+        MC.same_bits(f"pool {(h, w, k, s)}", ref, want.astype(np.float32))
 
 
 @pytest.mark.parametrize("hw", D.SM_HW)
@@ -229,62 +230,48 @@ def test_fp32_emulations_pass_every_case():
 
 
 # ---- argument checks: every IDB_REQUIRE of idb_mtcnn.hip answers before any HIP call -------------------------------------------------
-P = 1 << 20              # any non-null address: none of these calls dereferences it
-EINVAL = -1
-
-
-def _refused(lib, rc, text):
-    msg = lib.idb_last_error()
-    assert rc == EINVAL and text.encode() in msg, (rc, msg)
+P = MC.P16
 
 
 def test_area_argument_checks(lib):
     f = lib.idb_crop_resize_area_u8
     ok = dict(src=P, batch=2, h=61, w=45, c=3, boxes=P, n=2, out=P, oh=24, ow=24)
-    call = lambda **kw: (lambda a: f(a["src"], a["batch"], a["h"], a["w"], a["c"], a["boxes"], a["n"], a["out"], a["oh"], a["ow"], 127.5, 0.0078125,   # noqa: E731
-                                     None))({**ok, **kw})
-    assert call(n=0) == 0                                              # nothing to do: OK, no launch
-    for kw in (dict(src=None), dict(boxes=None), dict(out=None), dict(batch=0), dict(h=0), dict(w=0), dict(c=0), dict(n=-1), dict(oh=0), dict(ow=0),
-               dict(h=-3), dict(src=None, n=0)):
-        _refused(lib, call(**kw), "idb_crop_resize_area_u8: bad arguments")
-    _refused(lib, call(h=1 << 16, w=1 << 15), "idb_crop_resize_area_u8: image plane or box count too large")
-    _refused(lib, call(n=(1 << 28) + 1), "idb_crop_resize_area_u8: image plane or box count too large")
-    _refused(lib, call(n=1 << 28, c=4, oh=1024, ow=1024), "idb_crop_resize_area_u8: too many outputs")
+    call = lambda a: f(a["src"], a["batch"], a["h"], a["w"], a["c"], a["boxes"], a["n"], a["out"], a["oh"], a["ow"], 127.5, 0.0078125, None)   # noqa: E731
+    assert call({**ok, "n": 0}) == 0                                   # nothing to do: OK, no launch
+    MC.refused(lib, call, ok, (dict(src=None), dict(boxes=None), dict(out=None), dict(batch=0), dict(h=0), dict(w=0), dict(c=0), dict(n=-1), dict(oh=0),
+                               dict(ow=0), dict(h=-3), dict(src=None, n=0)), "idb_crop_resize_area_u8: bad arguments")
+    MC.refused(lib, call, ok, (dict(h=1 << 16, w=1 << 15), dict(n=(1 << 28) + 1)), "idb_crop_resize_area_u8: image plane or box count too large")
+    MC.refused(lib, call, ok, (dict(n=1 << 28, c=4, oh=1024, ow=1024),), "idb_crop_resize_area_u8: too many outputs")
 
 
 def test_conv_argument_checks(lib):
     f = lib.idb_conv2d_f32
     ok = dict(x=P, w=P, bias=None, slope=None, y=P, batch=2, cin=3, h=5, w_=7, cout=4, kh=3, kw=3)
-    call = lambda **kw: (lambda a: f(a["x"], a["w"], a["bias"], a["slope"], a["y"], a["batch"], a["cin"], a["h"], a["w_"], a["cout"], a["kh"], a["kw"],   # noqa: E731
-                                     None))({**ok, **kw})
-    for kw in (dict(x=None), dict(w=None), dict(y=None), dict(batch=0), dict(cin=0), dict(cout=0), dict(kh=0), dict(kw=0), dict(h=2), dict(w_=2),
-               dict(h=0), dict(batch=-1)):
-        _refused(lib, call(**kw), "idb_conv2d_f32: bad arguments")
-    _refused(lib, call(h=1 << 16, w_=1 << 15, kh=1, kw=1), "idb_conv2d_f32: plane or filter too large")
-    _refused(lib, call(cin=1 << 20, h=64, w_=64, kh=64, kw=32), "idb_conv2d_f32: plane or filter too large")
-    _refused(lib, call(batch=1 << 20, cout=1 << 20, h=32, w_=32, kh=1, kw=1), "idb_conv2d_f32: too many outputs")
+    call = lambda a: f(a["x"], a["w"], a["bias"], a["slope"], a["y"], a["batch"], a["cin"], a["h"], a["w_"], a["cout"], a["kh"], a["kw"], None)   # noqa: E731
+    MC.refused(lib, call, ok, (dict(x=None), dict(w=None), dict(y=None), dict(batch=0), dict(cin=0), dict(cout=0), dict(kh=0), dict(kw=0), dict(h=2),
+                               dict(w_=2), dict(h=0), dict(batch=-1)), "idb_conv2d_f32: bad arguments")
+    MC.refused(lib, call, ok, (dict(h=1 << 16, w_=1 << 15, kh=1, kw=1), dict(cin=1 << 20, h=64, w_=64, kh=64, kw=32)), "idb_conv2d_f32: plane or filter too large")
+    MC.refused(lib, call, ok, (dict(batch=1 << 20, cout=1 << 20, h=32, w_=32, kh=1, kw=1),), "idb_conv2d_f32: too many outputs")
 
 
 def test_pool_argument_checks(lib):
     f = lib.idb_maxpool2d_f32
     ok = dict(x=P, y=P, planes=4, h=9, w=9, k=3, s=2)
-    call = lambda **kw: (lambda a: f(a["x"], a["y"], a["planes"], a["h"], a["w"], a["k"], a["s"], None))({**ok, **kw})   # noqa: E731
-    for kw in (dict(x=None), dict(y=None), dict(planes=0), dict(h=0), dict(w=0), dict(k=0), dict(s=0), dict(k=-2)):
-        _refused(lib, call(**kw), "idb_maxpool2d_f32: bad arguments")
-    for kw in (dict(h=1 << 16, w=1 << 15), dict(h=(1 << 30) + 1, w=1), dict(h=1, w=(1 << 30) + 1), dict(k=(1 << 20) + 1), dict(s=(1 << 20) + 1)):
-        _refused(lib, call(**kw), "idb_maxpool2d_f32: plane, window or stride too large")
-    _refused(lib, call(planes=1 << 30, h=1 << 10, w=1 << 10, k=1, s=1), "idb_maxpool2d_f32: too many outputs")
+    call = lambda a: f(a["x"], a["y"], a["planes"], a["h"], a["w"], a["k"], a["s"], None)   # noqa: E731
+    MC.refused(lib, call, ok, (dict(x=None), dict(y=None), dict(planes=0), dict(h=0), dict(w=0), dict(k=0), dict(s=0), dict(k=-2)), "idb_maxpool2d_f32: bad arguments")
+    MC.refused(lib, call, ok, (dict(h=1 << 16, w=1 << 15), dict(h=(1 << 30) + 1, w=1), dict(h=1, w=(1 << 30) + 1), dict(k=(1 << 20) + 1), dict(s=(1 << 20) + 1)),
+               "idb_maxpool2d_f32: plane, window or stride too large")
+    MC.refused(lib, call, ok, (dict(planes=1 << 30, h=1 << 10, w=1 << 10, k=1, s=1),), "idb_maxpool2d_f32: too many outputs")
 
 
 def test_softmax_pairs_argument_checks(lib):
-    f = lib.idb_softmax_pairs_f32
-    for args in ((None, P, 3, 5), (P, None, 3, 5), (P, P, 0, 5), (P, P, 3, 0), (P, P, -1, 5)):
-        _refused(lib, f(*args, None), "idb_softmax_pairs_f32: bad arguments")
-    _refused(lib, f(P, P, 1 << 30, 1 << 30, None), "idb_softmax_pairs_f32: too many outputs")
+    ok = dict(x=P, y=P, b=3, hw=5)
+    call = lambda a: lib.idb_softmax_pairs_f32(a["x"], a["y"], a["b"], a["hw"], None)   # noqa: E731
+    MC.refused(lib, call, ok, (dict(x=None), dict(y=None), dict(b=0), dict(hw=0), dict(b=-1)), "idb_softmax_pairs_f32: bad arguments")
+    MC.refused(lib, call, ok, (dict(b=1 << 30, hw=1 << 30),), "idb_softmax_pairs_f32: too many outputs")
 
 
 def test_nms_mask_argument_checks(lib):
-    f = lib.idb_nms_mask
-    for args in ((None, P, 5, P), (P, P, 5, None), (P, None, 0, P), (P, P, -1, P), (P, P, (1 << 20) + 1, P)):
-        boxes, image, n, mask = args
-        _refused(lib, f(boxes, image, n, 0.5, 0, 0, mask, None), "idb_nms_mask: bad arguments")
+    ok = dict(boxes=P, image=P, n=5, mask=P)
+    call = lambda a: lib.idb_nms_mask(a["boxes"], a["image"], a["n"], 0.5, 0, 0, a["mask"], None)   # noqa: E731
+    MC.refused(lib, call, ok, (dict(boxes=None), dict(mask=None), dict(image=None, n=0), dict(n=-1), dict(n=(1 << 20) + 1)), "idb_nms_mask: bad arguments")

@@ -18,51 +18,21 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import detect_matrix as D  # noqa: E402
+import matrix_common as MC  # noqa: E402
 from faceposegenerator_amd import _lib as L  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-G = D.GUARD
-_WORST = {}             # kernel -> (worst err / bound, where)
-_COUNT = {}             # kernel -> launches
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _note(kernel, ratio, where, launches=2):
-    _COUNT[kernel] = _COUNT.get(kernel, 0) + launches
-    if kernel not in _WORST or ratio > _WORST[kernel][0]:
-        _WORST[kernel] = (ratio, where)
-
-
-class _Out:
-    """n fp32 outputs between guards."""
-
-    def __init__(self, n):
-        self.n = n
-        self.buf = torch.full((n + 2 * G,), D.NAN_BITS, dtype=torch.int32, device=DEV)
-        self.ptr = self.buf.data_ptr() + 4 * G
-
-    def result(self, what):
-        host = self.buf.cpu().numpy()
-        assert (host[:G] == D.NAN_BITS).all() and (host[G + self.n:] == D.NAN_BITS).all(), f"{what}: guard elements overwritten"
-        return host[G:G + self.n].view(np.float32)
+W = MC.Worst("detect matrix", launches=True)
 
 
 def _twice(n, launch, what):
     """launch(out pointer) into two separate guarded buffers; the results must be bit-equal.  Returns the first."""
-    a, b = _Out(n), _Out(n)
+    a, b = MC.Guarded(n), MC.Guarded(n)
     launch(a.ptr)
     launch(b.ptr)
     torch.cuda.synchronize()
-    ra, rb = a.result(what), b.result(what)
+    ra, rb = a.f32(what), b.f32(what)
     assert np.array_equal(ra.view(np.uint32), rb.view(np.uint32)), f"{what}: a relaunch gave different bits"
     return ra
 
@@ -71,51 +41,48 @@ def _twice(n, launch, what):
 def _area(lib, img_d, shape, boxes_np, oh, ow, what, sub=D.SUB, mul=D.MUL):
     b, h, w, c = shape
     n = boxes_np.shape[0]
-    bx = _dev(boxes_np if n else np.zeros((1, 5), np.int32))
+    bx = MC.dev(boxes_np if n else np.zeros((1, 5), np.int32))
 
     def launch(ptr):
-        L.check(lib.idb_crop_resize_area_u8(img_d.data_ptr(), b, h, w, c, bx.data_ptr(), n, ptr, oh, ow, sub, mul, _stream()), what)
+        L.check(lib.idb_crop_resize_area_u8(img_d.data_ptr(), b, h, w, c, bx.data_ptr(), n, ptr, oh, ow, sub, mul, MC.stream()), what)
     return _twice(n * c * oh * ow, launch, what).reshape(n, c, oh, ow)
 
 
 def _conv(lib, x, wt, bias, slope, what):
     b, cin, h, w = x.shape
     cout, _, kh, kw = wt.shape
-    xd, wd = _dev(x), _dev(wt)
-    bd, sd = (None if bias is None else _dev(bias)), (None if slope is None else _dev(slope))
+    xd, wd = MC.dev(x), MC.dev(wt)
+    bd, sd = (None if bias is None else MC.dev(bias)), (None if slope is None else MC.dev(slope))
 
     def launch(ptr):
         L.check(lib.idb_conv2d_f32(xd.data_ptr(), wd.data_ptr(), None if bd is None else bd.data_ptr(), None if sd is None else sd.data_ptr(), ptr,
-                                   b, cin, h, w, cout, kh, kw, _stream()), what)
+                                   b, cin, h, w, cout, kh, kw, MC.stream()), what)
     oh, ow = h - kh + 1, w - kw + 1
     return _twice(b * cout * oh * ow, launch, what).reshape(b, cout, oh, ow)
 
 
 def _pool(lib, x, k, s, what):
     p, h, w = x.shape
-    xd = _dev(x)
+    xd = MC.dev(x)
     oh, ow = D.pool_outputs(h, k, s), D.pool_outputs(w, k, s)
 
     def launch(ptr):
-        L.check(lib.idb_maxpool2d_f32(xd.data_ptr(), ptr, p, h, w, k, s, _stream()), what)
+        L.check(lib.idb_maxpool2d_f32(xd.data_ptr(), ptr, p, h, w, k, s, MC.stream()), what)
     return _twice(p * oh * ow, launch, what).reshape(p, oh, ow)
 
 
 def _softmax(lib, x, what):
     b, _, hw = x.shape
-    xd = _dev(x)
+    xd = MC.dev(x)
 
     def launch(ptr):
-        L.check(lib.idb_softmax_pairs_f32(xd.data_ptr(), ptr, b, hw, _stream()), what)
+        L.check(lib.idb_softmax_pairs_f32(xd.data_ptr(), ptr, b, hw, MC.stream()), what)
     return _twice(b * hw, launch, what).reshape(b, hw)
 
 
 def _check_conv(got, x, wt, bias, slope, what):
     ref, bound, _ = D.conv_reference(x, wt, bias, slope)
-    res = D.check(got, ref, bound)
-    print(D.describe(what, res))
-    assert res[0], D.describe(what, res)
-    _note("idb_conv2d_f32", res[1], what)
+    W.judge("idb_conv2d_f32", what, got, ref, bound, 2)
 
 
 def _check_softmax(got, x, what, thr_indices=(0, 1)):
@@ -124,8 +91,8 @@ def _check_softmax(got, x, what, thr_indices=(0, 1)):
     worst_ulp = float((np.abs(got.astype(np.float64) - ref) / D.ulp32(ref)).max())
     print(f"{D.describe(what, res)}; {worst_ulp:.3f} ulp of p1, bar {bar:.3f} ulp (emulation {emu:.3f})")
     assert res[0], D.describe(what, res)
-    _note("idb_softmax_pairs_f32", res[1], what)
-    _note("idb_softmax_pairs_f32 [ulp of p1]", worst_ulp, what, 0)
+    W.note("idb_softmax_pairs_f32", res[1], what, 2)
+    W.note("idb_softmax_pairs_f32 [ulp of p1]", worst_ulp, what)
     for ti in thr_indices:
         g, r, decided = D.decisions(got, ref, bound, ti)
         assert (~decided).mean() <= D.UNDECIDED_CAP, f"{what}: {int((~decided).sum())} of {decided.size} undecided at threshold {ti}"
@@ -136,7 +103,7 @@ def _check_softmax(got, x, what, thr_indices=(0, 1)):
 # ---- the cases -----------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def images():
-    return {k: (_dev(v), v.shape) for k, v in D.area_images().items()}
+    return {k: (MC.dev(v), v.shape) for k, v in D.area_images().items()}
 
 
 @pytest.mark.parametrize("case", D.area_cases(), ids=lambda c: c.name)
@@ -144,10 +111,7 @@ def test_area(lib, images, case):
     img_d, shape = images[case.image]
     got = _area(lib, img_d, shape, case.boxes_np, case.oh, case.ow, case.name)
     ref, bound = D.area_reference(D.area_images()[case.image], case)
-    res = D.check(got, ref, bound)
-    print(D.describe(case.name, res))
-    assert res[0], D.describe(case.name, res)
-    _note("idb_crop_resize_area_u8", res[1], case.name)
+    W.judge("idb_crop_resize_area_u8", case.name, got, ref, bound, 2)
 
 
 @pytest.mark.parametrize("case", D.conv_cases(), ids=lambda c: c.name)
@@ -162,26 +126,25 @@ def test_pool_grid(lib):
     cases = D.pool_cases()
     inputs = [D.pool_inputs(*c) for c in cases]
     refs = [D.pool_reference(x, c[2], c[3]) for x, c in zip(inputs, cases)]
-    xin = _dev(np.concatenate([x.reshape(-1) for x in inputs]))
+    xin = MC.dev(np.concatenate([x.reshape(-1) for x in inputs]))
     in_off = np.cumsum([0] + [x.size for x in inputs])
-    out_off, pos = [], G
+    out_off, pos = [], MC.GUARD
     for r in refs:
         out_off.append(pos)
-        pos += r.size + G
-    bufs = [torch.full((pos,), D.NAN_BITS, dtype=torch.int32, device=DEV) for _ in range(2)]
+        pos += r.size + MC.GUARD
+    bufs = [torch.full((pos,), D.NAN32, dtype=torch.int32, device=MC.DEV) for _ in range(2)]
     for buf in bufs:
         for c, x, i0, o0 in zip(cases, inputs, in_off, out_off):
-            L.check(lib.idb_maxpool2d_f32(xin.data_ptr() + 4 * int(i0), buf.data_ptr() + 4 * o0, x.shape[0], c[0], c[1], c[2], c[3], _stream()), f"pool {c}")
+            L.check(lib.idb_maxpool2d_f32(xin.data_ptr() + 4 * int(i0), buf.data_ptr() + 4 * o0, x.shape[0], c[0], c[1], c[2], c[3], MC.stream()), f"pool {c}")
     torch.cuda.synchronize()
     host = [b.cpu().numpy() for b in bufs]
     assert np.array_equal(host[0], host[1]), "pool: a relaunch gave different bits"
     written = np.zeros(pos, bool)
     for c, r, o0 in zip(cases, refs, out_off):
         written[o0:o0 + r.size] = True
-        ok, idx = D.bit_equal(host[0][o0:o0 + r.size].view(np.float32).reshape(r.shape), r)
-        assert ok, f"pool (h, w, k, stride) = {c}: element {idx} differs from the reference"
-    assert (host[0][~written] == D.NAN_BITS).all(), "pool: guard elements overwritten"
-    _note("idb_maxpool2d_f32", 0.0, "bit-equal on every case", 2 * len(cases))
+        MC.same_bits(f"pool (h, w, k, stride) = {c}", host[0][o0:o0 + r.size].view(np.float32).reshape(r.shape), r)
+    assert (host[0][~written] == D.NAN32).all(), "pool: guard elements overwritten"
+    W.note("idb_maxpool2d_f32", 0.0, "bit-equal on every case", 2 * len(cases))
 
 
 @pytest.mark.parametrize("hw", D.SM_HW)
@@ -195,17 +158,14 @@ def test_nms_mask(lib, case):
     from faceposegenerator_amd import mtcnn as M
     boxes, image, scores = D.nms_inputs(case)
     n, words = case.n, case.words
-    bd, imd = _dev(boxes), (_dev(image) if case.with_image else None)
-    guard = D.WORD_GUARD - (1 << 64)
-    bufs = [torch.full((n * words + 2 * G,), guard, dtype=torch.int64, device=DEV) for _ in range(2)]
+    bd, imd = MC.dev(boxes), (MC.dev(image) if case.with_image else None)
+    bufs = [MC.Guarded(n * words, 8, pattern=D.WORD_GUARD) for _ in range(2)]
     for buf in bufs:
-        L.check(lib.idb_nms_mask(bd.data_ptr(), None if imd is None else imd.data_ptr(), n, case.thr, int(case.method == "Min"), int(case.plus_one),
-                                 buf.data_ptr() + 8 * G, _stream()), case.name)
+        L.check(lib.idb_nms_mask(bd.data_ptr(), MC.ptr(imd), n, case.thr, int(case.method == "Min"), int(case.plus_one), buf.ptr, MC.stream()), case.name)
     torch.cuda.synchronize()
-    host = [b.cpu().numpy().view(np.uint64) for b in bufs]
+    host = [b.raw(case.name) for b in bufs]
     assert np.array_equal(host[0], host[1]), f"{case.name}: a relaunch gave different bits"
-    assert (host[0][:G] == np.uint64(D.WORD_GUARD)).all() and (host[0][G + n * words:] == np.uint64(D.WORD_GUARD)).all(), f"{case.name}: guard words overwritten"
-    mask = host[0][G:G + n * words].reshape(n, words)
+    mask = host[0].reshape(n, words)
     want = D.nms_mask_fp32(case, boxes, image)
     diff = np.argwhere(mask != want)
     assert diff.size == 0, f"{case.name}: word {diff[0].tolist()} is {int(mask[tuple(diff[0])]):#x}, the fp32 restatement has {int(want[tuple(diff[0])]):#x}"
@@ -218,7 +178,7 @@ def test_nms_mask(lib, case):
     idxs = image if case.with_image else np.zeros(n, np.int32)
     kept = D.bnms_order(D.host_scan(mask), idxs, scores)
     assert np.array_equal(kept, M._batched_nms(boxes, scores, idxs, case.thr, case.method, case.plus_one)), f"{case.name}: the scan keeps other boxes"
-    _note("idb_nms_mask", 0.0, "bit-equal on every case")
+    W.note("idb_nms_mask", 0.0, "bit-equal on every case", 2)
 
 
 # ---- one chained walk per network ----------------------------------------------------------------------------------------------------
@@ -238,8 +198,7 @@ def test_chain(lib, images, net):
     img_d, shape = images[case.image]
     x = _area(lib, img_d, shape, case.boxes_np, case.oh, case.ow, case.name)
     ref, bound = D.area_reference(D.area_images()[case.image], case)
-    res = D.check(x, ref, bound)
-    assert res[0], D.describe(case.name, res)
+    MC.within(case.name, x, ref, bound)
     for l in {"pnet": M.PNET, "rnet": M.RNET, "onet": M.ONET}[net]:
         if l[0] == "conv":
             what = f"chain {net} {l[1]} {x.shape}"
@@ -250,8 +209,7 @@ def test_chain(lib, images, net):
             what = f"chain {net} pool {l[1:]} {x.shape}"
             b, c, h, w = x.shape
             y = _pool(lib, x.reshape(b * c, h, w), l[1], l[2], what)
-            ok, idx = D.bit_equal(y, D.pool_reference(x.reshape(b * c, h, w), l[1], l[2]))
-            assert ok, f"{what}: element {idx} differs from the reference"
+            MC.same_bits(what, y, D.pool_reference(x.reshape(b * c, h, w), l[1], l[2]))
             assert y.shape[1:] == (M.pool_out(h, l[1], l[2]), M.pool_out(w, l[1], l[2]))
             y = y.reshape(b, c, *y.shape[1:])
         x = np.ascontiguousarray(y)
@@ -280,5 +238,4 @@ def test_chain(lib, images, net):
 
 
 def test_summary():
-    for k in sorted(_WORST):
-        print(f"detect matrix: {k}: {_COUNT[k]} launches, worst err / bound {_WORST[k][0]:.4f} ({_WORST[k][1]})")
+    W.show()

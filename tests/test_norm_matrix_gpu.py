@@ -42,6 +42,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import matrix_common as MC  # noqa: E402
 import norm_matrix as NM  # noqa: E402
 from faceposegenerator_amd import _lib as L  # noqa: E402
 
@@ -55,10 +56,6 @@ G = NM.GUARD_ROWS
 _WORST = defaultdict(lambda: [0, 0.0, ""])        # (op, dtype, recipe) -> [launches, worst ratio, where]
 _SYNC = {}
 _T0 = time.time()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _sync_counters():
@@ -101,12 +98,12 @@ class _Gn:
         if fp8:
             rc = self.lib.idb_groupnorm_fp8(self.x0.data_ptr(), c.c0, x1, c.c1, c.batch, c.hw, c.groups, c.eps, self.gamma.data_ptr(), self.beta.data_ptr(),
                                             int(c.silu), optr, FP8_INV_SCALE, NM.IDB_DT[self.dtype], self.ws.data_ptr(), self.ws_bytes,
-                                            None if pin is None else pin.data_ptr(), pch, _stream())
+                                            None if pin is None else pin.data_ptr(), pch, MC.stream())
         else:
             rc = self.lib.idb_groupnorm(self.x0.data_ptr(), c.c0, x1, c.c1, c.batch, c.hw, c.groups, c.eps, self.gamma.data_ptr(), self.beta.data_ptr(),
                                         int(c.silu), optr, NM.IDB_DT[self.dtype], self.ws.data_ptr(), self.ws_bytes,
                                         None if sync is None else sync.data_ptr(), 0 if sync is None else sync.numel(),
-                                        None if pin is None else pin.data_ptr(), pch, _stream())
+                                        None if pin is None else pin.data_ptr(), pch, MC.stream())
         L.check(rc, f"groupnorm {c.name}")
 
     def run(self, sync=None, pin=None, fp8=False):
@@ -128,7 +125,7 @@ class _Gn:
         part = torch.full((self.ws_bytes // 4,), float("nan"), dtype=torch.float32, device=DEV)
         chunks = C.c_int32(-1)
         L.check(self.lib.idb_groupnorm_stats(self.x0.data_ptr(), c.c0, self.x1.data_ptr() if c.c1 else None, c.c1, c.batch, c.hw, c.groups, part.data_ptr(),
-                                             self.ws_bytes, C.byref(chunks), NM.IDB_DT[self.dtype], _stream()), f"groupnorm_stats {c.name}")
+                                             self.ws_bytes, C.byref(chunks), NM.IDB_DT[self.dtype], MC.stream()), f"groupnorm_stats {c.name}")
         torch.cuda.synchronize()
         return part, chunks.value
 
@@ -290,7 +287,7 @@ def test_layernorm_matrix(lib, dtype):
                 ref, bnd = NM.ln_bound(x, gamma, beta, 1e-5, dtype, recipe)
                 xt, g32, b32 = x.to(NM.TDT[dtype]), gamma.float(), beta.float()
                 obuf = torch.full((rows + 2 * G, c), NM.CANARY, dtype=torch.int16, device=DEV)
-                L.check(lib.idb_layernorm(xt.data_ptr(), obuf.data_ptr() + G * c * 2, rows, c, 1e-5, g32.data_ptr(), b32.data_ptr(), NM.IDB_DT[dtype], _stream()))
+                L.check(lib.idb_layernorm(xt.data_ptr(), obuf.data_ptr() + G * c * 2, rows, c, 1e-5, g32.data_ptr(), b32.data_ptr(), NM.IDB_DT[dtype], MC.stream()))
                 torch.cuda.synchronize()
                 assert bool((obuf[:G] == NM.CANARY).all()) and bool((obuf[-G:] == NM.CANARY).all()), f"layernorm {rows}x{c}: a guard row lost its canary"
                 ok, ratio, nbad = NM.check(obuf[G:-G].view(NM.TDT[dtype]), ref, bnd)
@@ -310,7 +307,7 @@ def test_softmax_matrix(lib, dtype):
                 ref, bnd = NM.sm_bound(x, dtype)
                 buf = torch.full((rows + 2 * G, cols), NM.CANARY, dtype=torch.int16, device=DEV)
                 buf[G:-G] = x.to(NM.TDT[dtype]).view(torch.int16)
-                L.check(lib.idb_softmax_rows(buf.data_ptr() + G * cols * 2, rows, cols, NM.IDB_DT[dtype], _stream()))
+                L.check(lib.idb_softmax_rows(buf.data_ptr() + G * cols * 2, rows, cols, NM.IDB_DT[dtype], MC.stream()))
                 torch.cuda.synchronize()
                 assert bool((buf[:G] == NM.CANARY).all()) and bool((buf[-G:] == NM.CANARY).all()), f"softmax {rows}x{cols}: a guard row lost its canary"
                 ok, ratio, nbad = NM.check(buf[G:-G].view(NM.TDT[dtype]), ref, bnd)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import matrix_common as MC  # noqa: E402
 import metrics_oracle as O  # noqa: E402
 import pair_matrix as P  # noqa: E402
 
@@ -151,37 +152,41 @@ def test_knn_insert_is_the_kernels_list():
 
 
 # ---- argument checks: answered before any HIP call -----------------------------------------------------------------------------------------
-A = 1 << 20              # any non-null 16-byte aligned address: none of these calls dereferences it
+A = MC.P16
 
 
-def _refused(lib, rc, text):
-    msg = lib.idb_last_error()
-    assert rc == -1 and text.encode() in msg, (rc, msg)
+def _entries(lib):
+    """The five entries on the accepted argument set of each: the operand sizes, the workspace pointer `ws` and its size `sz`."""
+    from faceposegenerator_amd import _lib as L
+    return {L.IDB_PAIR_DIST2: lambda a: lib.idb_pair_dist2(A, a["na"], A, a["nb"], a["d"], A, A, a["ws"], a["sz"], None),
+            L.IDB_PAIR_KNN: lambda a: lib.idb_pair_knn_radii(A, a["na"], a["d"], A, a["kth"], A, a["ws"], a["sz"], None),
+            L.IDB_PAIR_PRDC: lambda a: lib.idb_pair_prdc_counts(A, a["na"], A, a["nb"], a["d"], A, A, A, A, A, A, a["ws"], a["sz"], None),
+            L.IDB_PAIR_NEAREST: lambda a: lib.idb_pair_nearest(A, a["na"], A, a["nb"], a["d"], A, a["excl"], A, A, a["ws"], a["sz"], None),
+            L.IDB_PAIR_POLY: lambda a: lib.idb_pair_poly_sums(A, a["na"], A, a["nb"], a["d"], a["ix"], A, a["s"], a["m"], 1.0, 1.0, A, a["ws"], a["sz"], None)}
+
+
+OK = dict(na=300, nb=200, d=8, kth=6, excl=0, ix=A, s=2, m=300, ws=A, sz=1 << 24)
 
 
 def test_workspace_must_be_16_byte_aligned_and_large_enough(lib):
     from faceposegenerator_amd import _lib as L
     q = lib.idb_pair_workspace_bytes
-    need = {m: q(m, 300, 200, 2) for m in (L.IDB_PAIR_DIST2, L.IDB_PAIR_KNN, L.IDB_PAIR_PRDC, L.IDB_PAIR_NEAREST, L.IDB_PAIR_POLY)}
-    assert all(v > 0 and v % 256 == 0 for v in need.values())
-    for ws, size in ((A + 4, 1 << 24), (A + 8, 1 << 24), (A, None)):
-        sz = lambda m: need[m] - 1 if size is None else size                # noqa: E731
-        _refused(lib, lib.idb_pair_dist2(A, 300, A, 200, 8, A, A, ws, sz(L.IDB_PAIR_DIST2), None), "workspace")
-        _refused(lib, lib.idb_pair_knn_radii(A, 300, 8, A, 6, A, ws, sz(L.IDB_PAIR_KNN), None), "workspace")
-        _refused(lib, lib.idb_pair_prdc_counts(A, 300, A, 200, 8, A, A, A, A, A, A, ws, sz(L.IDB_PAIR_PRDC), None), "workspace")
-        _refused(lib, lib.idb_pair_nearest(A, 300, A, 200, 8, A, 0, A, A, ws, sz(L.IDB_PAIR_NEAREST), None), "workspace")
-        _refused(lib, lib.idb_pair_poly_sums(A, 300, A, 300, 8, A, A, 2, 300, 1.0, 1.0, A, ws, sz(L.IDB_PAIR_POLY), None), "workspace")
+    for mode, call in _entries(lib).items():
+        ok = {**OK, "nb": 300} if mode == L.IDB_PAIR_POLY else OK             # the subsets of 300 need 300 rows on both sides
+        need = q(mode, 300, 200, 2)
+        assert need > 0 and need % 256 == 0
+        MC.refused(lib, call, ok, [dict(ws=A + 4), dict(ws=A + 8), dict(sz=need - 1)], "workspace")
 
 
 def test_degenerate_sizes_are_refused_or_accepted_by_rule(lib):
-    big = 1 << 24
-    _refused(lib, lib.idb_pair_knn_radii(A, 1, 4, A, 2, A, A, big, None), "kth")          # kth <= n
-    _refused(lib, lib.idb_pair_knn_radii(A, 8, 4, A, 9, A, A, big, None), "kth")
-    _refused(lib, lib.idb_pair_nearest(A, 1, A, 2, 4, A, 1, A, A, A, big, None), "exclude_diag")
-    _refused(lib, lib.idb_pair_poly_sums(A, 300, A, 280, 5, A, A, 1, 281, 1.0, 1.0, A, A, big, None), "subset size")   # m <= min(nx, ny)
-    _refused(lib, lib.idb_pair_poly_sums(A, 300, A, 280, 5, A, A, 21846, 2, 1.0, 1.0, A, A, big, None), "subsets")
-    _refused(lib, lib.idb_pair_poly_sums(A, 300, A, 280, 5, None, A, 1, 2, 1.0, 1.0, A, A, big, None), "null")
-    for f, args in ((lib.idb_pair_dist2, (A, (1 << 22) + 1, A, 4, 8, A, A, A, big, None)),
-                    (lib.idb_pair_prdc_counts, (A, 4, A, 4, (1 << 16) + 1, A, A, A, A, A, A, A, big, None)),
-                    (lib.idb_pair_knn_radii, (A, 4, 0, A, 1, A, A, big, None))):
-        _refused(lib, f(*args), " in 1..")
+    from faceposegenerator_amd import _lib as L
+    e = _entries(lib)
+    MC.refused(lib, e[L.IDB_PAIR_KNN], {**OK, "d": 4}, [dict(na=1, kth=2), dict(na=8, kth=9)], "kth")                 # kth <= n
+    MC.refused(lib, e[L.IDB_PAIR_NEAREST], {**OK, "d": 4}, [dict(na=1, nb=2, excl=1)], "exclude_diag")
+    poly = {**OK, "nb": 280, "d": 5}
+    MC.refused(lib, e[L.IDB_PAIR_POLY], poly, [dict(s=1, m=281)], "subset size")                                       # m <= min(nx, ny)
+    MC.refused(lib, e[L.IDB_PAIR_POLY], poly, [dict(s=21846, m=2)], "subsets")
+    MC.refused(lib, e[L.IDB_PAIR_POLY], poly, [dict(ix=None, s=1, m=2)], "null")
+    MC.refused(lib, e[L.IDB_PAIR_DIST2], OK, [dict(na=(1 << 22) + 1, nb=4)], " in 1..")
+    MC.refused(lib, e[L.IDB_PAIR_PRDC], OK, [dict(na=4, nb=4, d=(1 << 16) + 1)], " in 1..")
+    MC.refused(lib, e[L.IDB_PAIR_KNN], OK, [dict(na=4, d=0, kth=1)], " in 1..")

@@ -20,26 +20,15 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import matrix_common as MC  # noqa: E402
 import metrics_oracle as O  # noqa: E402
 import pair_matrix as P  # noqa: E402
 from faceposegenerator_amd import _lib as L  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-G = P.GUARD
 NAMES = [c.name for c in P.CASES]
-_WORST = {}             # mode -> (worst err / (TAU * scale), where)
-_COUNT = {}             # mode -> launches
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _note(mode, ratio, where):
-    if mode not in _WORST or ratio > _WORST[mode][0]:
-        _WORST[mode] = (ratio, where)
+W = MC.Worst("pair matrix", "err / (TAU * scale)", launches=True)
 
 
 class _In:
@@ -48,41 +37,10 @@ class _In:
     def __init__(self, a, off=False):
         a = np.ascontiguousarray(a)
         assert a.dtype.itemsize == 4
-        self.buf = torch.zeros(a.size + 8, dtype=torch.int32, device=DEV)
-        self.buf[int(off):int(off) + a.size] = torch.from_numpy(a.reshape(-1).view(np.int32)).to(DEV)
+        self.buf = torch.zeros(a.size + 8, dtype=torch.int32, device=MC.DEV)
+        self.buf[int(off):int(off) + a.size] = torch.from_numpy(a.reshape(-1).view(np.int32)).to(MC.DEV)
         self.ptr = self.buf.data_ptr() + 4 * int(off)
         assert self.buf.data_ptr() % 16 == 0 and self.ptr % 16 == (4 if off else 0)
-
-
-class _Out:
-    """n outputs of 4 or 8 bytes between guards."""
-
-    def __init__(self, n, dtype):
-        self.n, self.dtype = n, np.dtype(dtype)
-        wide = self.dtype.itemsize == 8
-        self.pattern = (P.NAN_BITS64 if wide else P.NAN_BITS)
-        self.buf = torch.full((n + 2 * G,), self.pattern, dtype=torch.int64 if wide else torch.int32, device=DEV)
-        self.ptr = self.buf.data_ptr() + self.dtype.itemsize * G
-
-    def result(self, what):
-        host = self.buf.cpu().numpy()
-        assert (host[:G] == self.pattern).all() and (host[G + self.n:] == self.pattern).all(), f"{what}: guard elements overwritten"
-        return host[G:G + self.n].view(self.dtype)
-
-
-class _Ws:
-    """Exactly `size` workspace bytes between guards."""
-
-    def __init__(self, size):
-        assert size > 0 and size % 4 == 0
-        self.size, self.words = size, size // 4
-        self.buf = torch.full((self.words + 2 * G,), P.NAN_BITS, dtype=torch.int32, device=DEV)
-        self.ptr = self.buf.data_ptr() + 4 * G
-        assert self.ptr % 16 == 0
-
-    def check(self, what):
-        host = self.buf.cpu().numpy()
-        assert (host[:G] == P.NAN_BITS).all() and (host[G + self.words:] == P.NAN_BITS).all(), f"{what}: the workspace's guards overwritten"
 
 
 class Gpu:
@@ -94,18 +52,18 @@ class Gpu:
     def _twice(self, mode, what, size_args, outs, launch):
         """launch(out pointers, ws pointer, ws bytes) twice into separate buffers; bit-equal; the first results as numpy arrays."""
         need = self.lib.idb_pair_workspace_bytes(*size_args)
-        assert need > 0, f"{what}: idb_pair_workspace_bytes{size_args} refused"
+        assert need > 0 and need % 4 == 0, f"{what}: idb_pair_workspace_bytes{size_args} refused"
         runs = []
         for _ in range(2):
-            bufs, ws = [_Out(n, dt) for n, dt in outs], _Ws(need)
-            L.check(launch([b.ptr for b in bufs], ws.ptr, ws.size), what)
+            bufs, ws = [MC.Guarded(n, np.dtype(dt).itemsize) for n, dt in outs], MC.Guarded(need // 4)
+            L.check(launch([b.ptr for b in bufs], ws.ptr, need), what)
             runs.append((bufs, ws))
         torch.cuda.synchronize()
-        _COUNT[mode] = _COUNT.get(mode, 0) + 2
+        W.launched(mode, 2)
         res = []
         for bufs, ws in runs:
-            ws.check(what)
-            res.append([b.result(what) for b in bufs])
+            ws.raw(what + ": the workspace")
+            res.append([b.raw(what).view(dt) for b, (_, dt) in zip(bufs, outs)])
         for x, y in zip(*res):
             assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), f"{what}: a relaunch gave different bits"
         return res[0]
@@ -117,14 +75,14 @@ class Gpu:
         na, nb, d = len(a), len(b), a.shape[1]
         ad, bd, sd = _In(a, self.mis == "a"), _In(b, self.mis == "b"), self._shift(shift)
         out, = self._twice("dist2", f"idb_pair_dist2 {na} x {nb} x {d}", (L.IDB_PAIR_DIST2, na, nb, 0), [(na * nb, np.float32)],
-                           lambda o, ws, sz: self.lib.idb_pair_dist2(ad.ptr, na, bd.ptr, nb, d, sd and sd.ptr, o[0], ws, sz, _stream()))
+                           lambda o, ws, sz: self.lib.idb_pair_dist2(ad.ptr, na, bd.ptr, nb, d, sd and sd.ptr, o[0], ws, sz, MC.stream()))
         return out.reshape(na, nb)
 
     def knn(self, x, shift, kths):
         n, d = x.shape
         xd, sd = _In(x, self.mis in ("a", "b")), self._shift(shift)
         return {kth: self._twice("knn", f"idb_pair_knn_radii {n} x {d} kth {kth}", (L.IDB_PAIR_KNN, n, 0, 0), [(n, np.float32)],
-                                 lambda o, ws, sz: self.lib.idb_pair_knn_radii(xd.ptr, n, d, sd and sd.ptr, kth, o[0], ws, sz, _stream()))[0]
+                                 lambda o, ws, sz: self.lib.idb_pair_knn_radii(xd.ptr, n, d, sd and sd.ptr, kth, o[0], ws, sz, MC.stream()))[0]
                 for kth in kths}
 
     def prdc(self, real, gen, shift, r2_real, r2_gen):
@@ -134,7 +92,7 @@ class Gpu:
         return self._twice("prdc", f"idb_pair_prdc_counts {nr} x {ng} x {d}", (L.IDB_PAIR_PRDC, nr, ng, 0),
                            [(ng, np.int32), (nr, np.int32), (nr, np.float32)],
                            lambda o, ws, sz: self.lib.idb_pair_prdc_counts(rd.ptr, nr, gd.ptr, ng, d, sd and sd.ptr, r2r.ptr, r2g.ptr, o[0], o[1], o[2],
-                                                                           ws, sz, _stream()))
+                                                                           ws, sz, MC.stream()))
 
     def nearest(self, a, b, shift, exclude_diag):
         na, nb, d = len(a), len(b), a.shape[1]
@@ -142,7 +100,7 @@ class Gpu:
         return self._twice("nearest", f"idb_pair_nearest {na} x {nb} x {d} exclude_diag {int(exclude_diag)}", (L.IDB_PAIR_NEAREST, na, nb, 0),
                            [(nb, np.float32), (nb, np.int32)],
                            lambda o, ws, sz: self.lib.idb_pair_nearest(ad.ptr, na, bd.ptr, nb, d, sd and sd.ptr, int(exclude_diag), o[0], o[1], ws, sz,
-                                                                       _stream()))
+                                                                       MC.stream()))
 
     def poly(self, x, y, ix, iy, gamma=1.0):
         (nx, d), ny, (s, m) = x.shape, len(y), ix.shape
@@ -150,7 +108,7 @@ class Gpu:
         dx, dy = _In(ix.astype(np.int32)), _In(iy.astype(np.int32))
         out, = self._twice("poly", f"idb_pair_poly_sums {nx} x {ny} x {d}, {s} subsets of {m}", (L.IDB_PAIR_POLY, m, 0, s), [(3 * s, np.float64)],
                            lambda o, ws, sz: self.lib.idb_pair_poly_sums(xd.ptr, nx, yd.ptr, ny, d, dx.ptr, dy.ptr, s, m, gamma, 1.0, o[0], ws, sz,
-                                                                         _stream()))
+                                                                         MC.stream()))
         return out.reshape(s, 3)
 
 
@@ -158,21 +116,21 @@ class Gpu:
 @pytest.mark.parametrize("mode", P.MODES[:4])
 @pytest.mark.parametrize("name", NAMES)
 def test_real_case(lib, name, mode):
-    P.run_real_case(Gpu(lib), name, mode, _note)
+    P.run_real_case(Gpu(lib), name, mode, W.note)
 
 
 def test_degenerate_sets(lib):
-    P.run_degenerate(Gpu(lib), _note)
+    P.run_degenerate(Gpu(lib), W.note)
 
 
 @pytest.mark.parametrize("which", ("forward", "reversed", "swapped", "exclude", "knn"))
 def test_integer_ties_across_passes_and_splits(lib, which):
-    P.run_ties(Gpu(lib), which, _note)
+    P.run_ties(Gpu(lib), which, W.note)
 
 
 @pytest.mark.parametrize("case", P.POLY_CASES, ids=lambda c: "x".join(map(str, c)))
 def test_poly_sums_exact(lib, case):
-    P.run_poly(Gpu(lib), case, _note)
+    P.run_poly(Gpu(lib), case, W.note)
 
 
 def test_kd_chunking(lib):
@@ -218,12 +176,8 @@ def test_misaligned_operand_gives_the_aligned_bits(lib, name, mis):
         _ALIGNED[name] = _every_mode(lib, name, None)
     for label, g, w in zip(_LABELS, _every_mode(lib, name, mis), _ALIGNED[name]):
         assert g.shape == w.shape and g.dtype == w.dtype
-        bits = np.dtype(f"u{g.dtype.itemsize}")
-        diff = np.argwhere(g.view(bits) != w.view(bits))
-        assert diff.size == 0, (f"{name}, `{mis}` misaligned, {label}: element {diff[0].tolist()} is {g[tuple(diff[0])]!r}, the aligned run has "
-                                f"{w[tuple(diff[0])]!r}: bound 0")
+        MC.same_bits(f"{name}, `{mis}` misaligned, {label} against the aligned run", g, w)
 
 
 def test_summary():
-    for k in sorted(_WORST):
-        print(f"pair matrix: {k}: {_COUNT.get(k, 0)} launches, worst err / (TAU * scale) {_WORST[k][0]:.4f} ({_WORST[k][1]})")
+    W.show()

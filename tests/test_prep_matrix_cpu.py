@@ -14,15 +14,12 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import matrix_common as MC  # noqa: E402
 import prep_matrix as P  # noqa: E402
 
 T64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64))   # noqa: E731
 F32, F64 = np.float32, np.float64
-_WORST = {}
-
-
-def _note(kernel, ratio):
-    _WORST[kernel] = max(_WORST.get(kernel, 0.0), ratio)
+W = MC.Worst("prep matrix, fp32 emulation")
 
 
 # ---- roundings -----------------------------------------------------------------------------------------------------------------------
@@ -333,7 +330,7 @@ def test_lora_emulation_passes(case):
         ref, bound = P.lora_reference(case, dt, e_scale=0.5)                # half the fp32 allowance, the whole rounding to T
         res = P.check(P.from_bits(P.emulate_lora(case, dt), dt).reshape(ref.shape), ref, bound)
         assert res[0], P.describe(f"{case.name} {dt}", res)
-        _note(f"idb_lora_merge{'_scaled' if case.scaled else ''} {dt}", res[1])
+        W.note(f"idb_lora_merge{'_scaled' if case.scaled else ''} {dt}", res[1])
 
 
 @pytest.mark.parametrize("case", P.FOLD_CASES, ids=lambda c: c.name)
@@ -343,7 +340,7 @@ def test_fold_emulation_passes(case):
         eu, ev = P.emulate_fold(case, dt)
         for name, res in (("u", P.check(eu, u, bu)), ("v", P.check(ev, v, bv))):
             assert res[0] and res[1] <= 0.5, P.describe(f"{case.name} {dt} {name}", res)
-            _note(f"idb_ln_fold_vectors {name} {dt}", res[1])
+            W.note(f"idb_ln_fold_vectors {name} {dt}", res[1])
 
 
 @pytest.mark.parametrize("case", P.cfg_cases(), ids=lambda c: c.name)
@@ -353,8 +350,8 @@ def test_cfg_emulation_passes(case):
     rp, r0 = P.check(ep, prev, bp), P.check(e0, x0, b0)
     assert rp[0] and rp[1] <= 0.5, P.describe(f"{case.name} latents", rp)
     assert r0[0], P.describe(f"{case.name} x0", r0)                         # sharp: see the module docstring
-    _note("idb_cfg_ddpm_step latents", rp[1])
-    _note("idb_cfg_ddpm_step x0", r0[1])
+    W.note("idb_cfg_ddpm_step latents", rp[1])
+    W.note("idb_cfg_ddpm_step x0", r0[1])
 
 
 @pytest.mark.parametrize("shape", P.VAE_SHAPES, ids=str)
@@ -365,134 +362,116 @@ def test_vae_emulation_passes(shape):
         res = P.check(z, ref, bound)
         assert res[0] and (res[1] <= 0.5 or not with_noise), P.describe(f"vae {shape} noise {with_noise}", res)      # one rounding: sharp
         assert np.array_equal(m.view(np.uint32), mean.view(np.uint32)) and np.array_equal(l2.view(np.uint32), lv.view(np.uint32))
-        _note("idb_vae_sample" + ("" if with_noise else " mode"), res[1])
+        W.note("idb_vae_sample" + ("" if with_noise else " mode"), res[1])
 
 
 def test_summary():
-    for k in sorted(_WORST):
-        print(f"prep matrix, fp32 emulation: {k}: worst err / bound {_WORST[k]:.4f}")
+    W.show()
 
 
 # ---- argument checks: every IDB_REQUIRE of the fourteen entry points answers before any HIP call ---------------------------------------
-P16 = 1 << 20            # any non-null 16-byte-aligned address: none of these calls dereferences it
-EINVAL = -1
+P16 = MC.P16
 BIG = 1 << 39
 
 
-@pytest.fixture(scope="module")
-def dts():
-    from faceposegenerator_amd import _lib
-    return _lib.IDB_F16, _lib.IDB_BF16
+def _pos(fn):
+    """The entry on an argument set's values: every `ok` below lists the arguments in the entry's order."""
+    return lambda a: fn(*a.values())
 
 
-def _refused(lib, fn, ok, variants, text):
-    """Every variant of the accepted argument set `ok` answers IDB_EINVAL with `text` in idb_last_error(), and launches nothing."""
-    before = lib.idb_launch_count()
-    for kw in variants:
-        args = {**ok, **kw}
-        rc = fn(*args.values())
-        msg = lib.idb_last_error()
-        assert rc == EINVAL and msg and text.encode() in msg, (kw, rc, msg)
-    assert lib.idb_launch_count() == before
-
-
-def _bad_dtypes(dts):
-    return [dict(dtype=d) for d in (-1, 99, max(dts) + 1) if d not in dts]
-
-
-def test_pack_conv_weight_argument_checks(lib, dts):
-    ok = dict(src=P16, dst=P16, cout=3, cin=5, taps=9, dtype=dts[0], stream=None)
+def test_pack_conv_weight_argument_checks(lib):
+    ok = dict(src=P16, dst=P16, cout=3, cin=5, taps=9, dtype=MC.IDB["f16"], stream=None)
     f = lib.idb_pack_conv_weight
-    _refused(lib, f, ok, _bad_dtypes(dts) + [dict(src=None), dict(dst=None), dict(cout=0), dict(cin=0), dict(taps=0), dict(cout=-1)], "idb_pack_conv_weight: bad args")
-    _refused(lib, f, ok, [dict(cout=1 << 13, cin=1 << 13, taps=1 << 13), dict(cout=2 ** 31 - 1, cin=2 ** 31 - 1, taps=2 ** 31 - 1), dict(cout=1 << 30, cin=1 << 9, taps=1)],
+    MC.refused(lib, _pos(f), ok, MC.BAD_DTYPES + [dict(src=None), dict(dst=None), dict(cout=0), dict(cin=0), dict(taps=0), dict(cout=-1)], "idb_pack_conv_weight: bad args")
+    MC.refused(lib, _pos(f), ok, [dict(cout=1 << 13, cin=1 << 13, taps=1 << 13), dict(cout=2 ** 31 - 1, cin=2 ** 31 - 1, taps=2 ** 31 - 1), dict(cout=1 << 30, cin=1 << 9, taps=1)],
              "idb_pack_conv_weight: 2^39")
 
 
-def test_pack_matrix_argument_checks(lib, dts):
+def test_pack_matrix_argument_checks(lib):
     for name, scaled in (("idb_pack_matrix", False), ("idb_pack_matrix_scaled", True)):
-        ok = dict(src=P16, dst=P16, rows=64, cols=5, geglu=1, **({"cs": P16} if scaled else {}), dtype=dts[1], stream=None)
+        ok = dict(src=P16, dst=P16, rows=64, cols=5, geglu=1, **({"cs": P16} if scaled else {}), dtype=MC.IDB["bf16"], stream=None)
         f = getattr(lib, name)
-        _refused(lib, f, ok, _bad_dtypes(dts) + [dict(src=None), dict(dst=None), dict(rows=0), dict(cols=0), dict(cols=-3)] + ([dict(cs=None)] if scaled else []),
+        MC.refused(lib, _pos(f), ok, MC.BAD_DTYPES + [dict(src=None), dict(dst=None), dict(rows=0), dict(cols=0), dict(cols=-3)] + ([dict(cs=None)] if scaled else []),
                  f"{name}: bad args")
-        _refused(lib, f, ok, [dict(rows=48), dict(rows=16), dict(rows=33)], f"{name}: GEGLU")
-        _refused(lib, f, ok, [dict(rows=1 << 20, cols=1 << 19), dict(rows=BIG, cols=1, geglu=0), dict(rows=1 << 32, cols=1 << 32), dict(rows=2 ** 63 - 1, cols=2 ** 63 - 1, geglu=0)],
+        MC.refused(lib, _pos(f), ok, [dict(rows=48), dict(rows=16), dict(rows=33)], f"{name}: GEGLU")
+        MC.refused(lib, _pos(f), ok, [dict(rows=1 << 20, cols=1 << 19), dict(rows=BIG, cols=1, geglu=0), dict(rows=1 << 32, cols=1 << 32), dict(rows=2 ** 63 - 1, cols=2 ** 63 - 1, geglu=0)],
                  f"{name}: 2^39")
 
 
-def test_lora_merge_argument_checks(lib, dts):
-    ok = dict(w=P16, a=P16, b=P16, dst=P16, rows=7, cols=37, rank=4, scale=0.5, dtype=dts[0], stream=None)
+def test_lora_merge_argument_checks(lib):
+    ok = dict(w=P16, a=P16, b=P16, dst=P16, rows=7, cols=37, rank=4, scale=0.5, dtype=MC.IDB["f16"], stream=None)
     f = lib.idb_lora_merge
-    _refused(lib, f, ok, _bad_dtypes(dts) + [dict(w=None), dict(a=None), dict(b=None), dict(dst=None), dict(rows=0), dict(cols=0), dict(rank=0), dict(rank=-1)],
+    MC.refused(lib, _pos(f), ok, MC.BAD_DTYPES + [dict(w=None), dict(a=None), dict(b=None), dict(dst=None), dict(rows=0), dict(cols=0), dict(rank=0), dict(rank=-1)],
              "idb_lora_merge: bad args")
-    _refused(lib, f, ok, [dict(rows=1 << 20, cols=1 << 19), dict(rows=1 << 62, cols=4)], "idb_lora_merge: 2^39")
-    ok = dict(w=P16, a=P16, b=P16, dst=P16, rows=7, cols=37, rank=4, scale=0.5, cs=P16, dtype=dts[1], stream=None)
+    MC.refused(lib, _pos(f), ok, [dict(rows=1 << 20, cols=1 << 19), dict(rows=1 << 62, cols=4)], "idb_lora_merge: 2^39")
+    ok = dict(w=P16, a=P16, b=P16, dst=P16, rows=7, cols=37, rank=4, scale=0.5, cs=P16, dtype=MC.IDB["bf16"], stream=None)
     f = lib.idb_lora_merge_scaled
-    _refused(lib, f, ok, _bad_dtypes(dts) + [dict(w=None), dict(dst=None), dict(cs=None), dict(rows=0), dict(cols=0), dict(rank=-1), dict(a=None), dict(b=None), dict(a=None, b=None)],
+    MC.refused(lib, _pos(f), ok, MC.BAD_DTYPES + [dict(w=None), dict(dst=None), dict(cs=None), dict(rows=0), dict(cols=0), dict(rank=-1), dict(a=None), dict(b=None), dict(a=None, b=None)],
              "idb_lora_merge_scaled: bad args")
-    _refused(lib, f, ok, [dict(rows=1 << 20, cols=1 << 19), dict(rows=1 << 62, cols=4, rank=0, a=None, b=None)], "idb_lora_merge_scaled: 2^39")
+    MC.refused(lib, _pos(f), ok, [dict(rows=1 << 20, cols=1 << 19), dict(rows=1 << 62, cols=4, rank=0, a=None, b=None)], "idb_lora_merge_scaled: 2^39")
 
 
-def test_tile_weight_argument_checks(lib, dts):
-    ok = dict(src=P16, dst=P16, n=17, k=128, dtype=dts[0], stream=None)
+def test_tile_weight_argument_checks(lib):
+    ok = dict(src=P16, dst=P16, n=17, k=128, dtype=MC.IDB["f16"], stream=None)
     f = lib.idb_tile_weight
-    _refused(lib, f, ok, _bad_dtypes(dts) + [dict(src=None), dict(dst=None), dict(n=0), dict(k=0), dict(k=96), dict(k=65), dict(src=P16 + 8), dict(dst=P16 + 2)],
+    MC.refused(lib, _pos(f), ok, MC.BAD_DTYPES + [dict(src=None), dict(dst=None), dict(n=0), dict(k=0), dict(k=96), dict(k=65), dict(src=P16 + 8), dict(dst=P16 + 2)],
              "idb_tile_weight: needs operand dtype")
-    _refused(lib, f, ok, [dict(n=1 << 33, k=64), dict(n=(1 << 33) - 15, k=64), dict(n=2 ** 63 - 1, k=64), dict(n=3, k=1 << 36)], "idb_tile_weight: 2^39")
+    MC.refused(lib, _pos(f), ok, [dict(n=1 << 33, k=64), dict(n=(1 << 33) - 15, k=64), dict(n=2 ** 63 - 1, k=64), dict(n=3, k=1 << 36)], "idb_tile_weight: 2^39")
     for n, k in P.TILE_SHAPES + ((1 << 20, 1 << 12),):
         assert lib.idb_tiled_weight_bytes(n, k) == P.tiled_bytes(n, k)
     assert lib.idb_tiled_weight_bytes(0, 64) == 0 and lib.idb_tiled_weight_bytes(5, 0) == 0
 
 
-def test_ln_fold_vectors_argument_checks(lib, dts):
-    ok = dict(w=P16, a=P16, b=P16, rank=4, scale=1.0, wq=P16, beta=P16, bias=P16, u=P16, v=P16, rows=96, cols=200, geglu=1, dtype=dts[0], stream=None)
+def test_ln_fold_vectors_argument_checks(lib):
+    ok = dict(w=P16, a=P16, b=P16, rank=4, scale=1.0, wq=P16, beta=P16, bias=P16, u=P16, v=P16, rows=96, cols=200, geglu=1, dtype=MC.IDB["f16"], stream=None)
     f = lib.idb_ln_fold_vectors
-    _refused(lib, f, ok, _bad_dtypes(dts) + [dict(w=None), dict(wq=None), dict(beta=None), dict(u=None), dict(v=None), dict(rows=0), dict(cols=0), dict(rank=-1), dict(rank=17),
+    MC.refused(lib, _pos(f), ok, MC.BAD_DTYPES + [dict(w=None), dict(wq=None), dict(beta=None), dict(u=None), dict(v=None), dict(rows=0), dict(cols=0), dict(rank=-1), dict(rank=17),
                                              dict(b=None)], "idb_ln_fold_vectors: bad args")
-    _refused(lib, f, ok, [dict(rows=48), dict(rows=100)], "idb_ln_fold_vectors: GEGLU")
-    _refused(lib, f, ok, [dict(rows=1 << 20, cols=1 << 19), dict(rows=1 << 33, cols=1, geglu=0), dict(rows=1 << 62, cols=1 << 62)], "idb_ln_fold_vectors: 2^39")
+    MC.refused(lib, _pos(f), ok, [dict(rows=48), dict(rows=100)], "idb_ln_fold_vectors: GEGLU")
+    MC.refused(lib, _pos(f), ok, [dict(rows=1 << 20, cols=1 << 19), dict(rows=1 << 33, cols=1, geglu=0), dict(rows=1 << 62, cols=1 << 62)], "idb_ln_fold_vectors: 2^39")
 
 
 def test_cfg_ddpm_step_argument_checks(lib):
     ok = dict(eps=P16, lat=P16, noise=None, coef=P16, x0=None, batch=2, c=3, hw=5, cfg=1, pred=0, stream=None)
     f = lib.idb_cfg_ddpm_step
-    _refused(lib, f, ok, [dict(eps=None), dict(lat=None), dict(coef=None), dict(batch=0), dict(c=0), dict(hw=0), dict(hw=-5)], "idb_cfg_ddpm_step: bad args")
-    _refused(lib, f, ok, [dict(pred=2), dict(pred=-1)], "idb_cfg_ddpm_step: prediction_type")
-    _refused(lib, f, ok, [dict(batch=1 << 13, c=1 << 13, hw=1 << 13), dict(batch=2 ** 31 - 1, c=2 ** 31 - 1, hw=2 ** 31 - 1)], "idb_cfg_ddpm_step: 2^39")
+    MC.refused(lib, _pos(f), ok, [dict(eps=None), dict(lat=None), dict(coef=None), dict(batch=0), dict(c=0), dict(hw=0), dict(hw=-5)], "idb_cfg_ddpm_step: bad args")
+    MC.refused(lib, _pos(f), ok, [dict(pred=2), dict(pred=-1)], "idb_cfg_ddpm_step: prediction_type")
+    MC.refused(lib, _pos(f), ok, [dict(batch=1 << 13, c=1 << 13, hw=1 << 13), dict(batch=2 ** 31 - 1, c=2 ** 31 - 1, hw=2 ** 31 - 1)], "idb_cfg_ddpm_step: 2^39")
 
 
 def test_vae_sample_argument_checks(lib):
     ok = dict(m=P16, noise=None, scale=0.18215, lat=P16, mean=None, lv=None, batch=2, c=3, hw=5, stream=None)
     f = lib.idb_vae_sample
-    _refused(lib, f, ok, [dict(m=None), dict(lat=None), dict(batch=0), dict(c=0), dict(hw=0), dict(c=-4)], "idb_vae_sample: bad args")
-    _refused(lib, f, ok, [dict(batch=1 << 13, c=1 << 13, hw=1 << 13), dict(batch=2 ** 31 - 1, c=2 ** 31 - 1, hw=2 ** 31 - 1), dict(batch=1, c=1 << 30, hw=1)], "idb_vae_sample: 2^39")
+    MC.refused(lib, _pos(f), ok, [dict(m=None), dict(lat=None), dict(batch=0), dict(c=0), dict(hw=0), dict(c=-4)], "idb_vae_sample: bad args")
+    MC.refused(lib, _pos(f), ok, [dict(batch=1 << 13, c=1 << 13, hw=1 << 13), dict(batch=2 ** 31 - 1, c=2 ** 31 - 1, hw=2 ** 31 - 1), dict(batch=1, c=1 << 30, hw=1)], "idb_vae_sample: 2^39")
 
 
-def test_postprocess_and_cast_argument_checks(lib, dts):
+def test_postprocess_and_cast_argument_checks(lib):
     ok = dict(x=P16, img=P16, u8=P16, count=257, stream=None)
     f = lib.idb_postprocess
-    _refused(lib, f, ok, [dict(x=None), dict(img=None, u8=None), dict(count=0), dict(count=-1)], "idb_postprocess: bad args")
-    _refused(lib, f, ok, [dict(count=BIG), dict(count=2 ** 63 - 1)], "idb_postprocess: 2^39")
-    ok = dict(x=P16, out=P16, count=257, dtype=dts[0], stream=None)
+    MC.refused(lib, _pos(f), ok, [dict(x=None), dict(img=None, u8=None), dict(count=0), dict(count=-1)], "idb_postprocess: bad args")
+    MC.refused(lib, _pos(f), ok, [dict(count=BIG), dict(count=2 ** 63 - 1)], "idb_postprocess: 2^39")
+    ok = dict(x=P16, out=P16, count=257, dtype=MC.IDB["f16"], stream=None)
     f = lib.idb_cast_f32
-    _refused(lib, f, ok, _bad_dtypes(dts) + [dict(x=None), dict(out=None), dict(count=0), dict(count=-7)], "idb_cast_f32: bad args")
-    _refused(lib, f, ok, [dict(count=BIG), dict(count=2 ** 63 - 1)], "idb_cast_f32: 2^39")
+    MC.refused(lib, _pos(f), ok, MC.BAD_DTYPES + [dict(x=None), dict(out=None), dict(count=0), dict(count=-7)], "idb_cast_f32: bad args")
+    MC.refused(lib, _pos(f), ok, [dict(count=BIG), dict(count=2 ** 63 - 1)], "idb_cast_f32: 2^39")
 
 
-def test_transpose_argument_checks(lib, dts):
-    ok = dict(x=P16, out=P16, batch=2, hw=3, c=5, dtype=dts[1], stream=None)
+def test_transpose_argument_checks(lib):
+    ok = dict(x=P16, out=P16, batch=2, hw=3, c=5, dtype=MC.IDB["bf16"], stream=None)
     f = lib.idb_nhwc_to_nchw_f32
-    _refused(lib, f, ok, _bad_dtypes(dts) + [dict(x=None), dict(out=None), dict(batch=0), dict(hw=0), dict(c=0)], "idb_nhwc_to_nchw_f32: bad args")
-    _refused(lib, f, ok, [dict(batch=1 << 13, hw=1 << 13, c=1 << 13), dict(batch=2 ** 31 - 1, hw=2 ** 31 - 1, c=2 ** 31 - 1)], "idb_nhwc_to_nchw_f32: 2^39")
+    MC.refused(lib, _pos(f), ok, MC.BAD_DTYPES + [dict(x=None), dict(out=None), dict(batch=0), dict(hw=0), dict(c=0)], "idb_nhwc_to_nchw_f32: bad args")
+    MC.refused(lib, _pos(f), ok, [dict(batch=1 << 13, hw=1 << 13, c=1 << 13), dict(batch=2 ** 31 - 1, hw=2 ** 31 - 1, c=2 ** 31 - 1)], "idb_nhwc_to_nchw_f32: 2^39")
     ok = dict(x=P16, out=P16, batch=2, hw=3, c=5, stream=None)
     f = lib.idb_f32_nhwc_to_nchw
-    _refused(lib, f, ok, [dict(x=None), dict(out=None), dict(batch=0), dict(hw=0), dict(c=0)], "idb_f32_nhwc_to_nchw: bad args")
-    _refused(lib, f, ok, [dict(batch=1 << 13, hw=1 << 13, c=1 << 13), dict(batch=2 ** 31 - 1, hw=2 ** 31 - 1, c=2 ** 31 - 1)], "idb_f32_nhwc_to_nchw: 2^39")
+    MC.refused(lib, _pos(f), ok, [dict(x=None), dict(out=None), dict(batch=0), dict(hw=0), dict(c=0)], "idb_f32_nhwc_to_nchw: bad args")
+    MC.refused(lib, _pos(f), ok, [dict(batch=1 << 13, hw=1 << 13, c=1 << 13), dict(batch=2 ** 31 - 1, hw=2 ** 31 - 1, c=2 ** 31 - 1)], "idb_f32_nhwc_to_nchw: 2^39")
 
 
-def test_embed_tokens_argument_checks(lib, dts):
-    ok = dict(ids=P16, tok=P16, pos=P16, out=P16, batch=2, n=3, dim=8, dtype=dts[0], stream=None)
+def test_embed_tokens_argument_checks(lib):
+    ok = dict(ids=P16, tok=P16, pos=P16, out=P16, batch=2, n=3, dim=8, dtype=MC.IDB["f16"], stream=None)
     f = lib.idb_embed_tokens
-    _refused(lib, f, ok, _bad_dtypes(dts) + [dict(ids=None), dict(tok=None), dict(pos=None), dict(out=None)], "idb_embed_tokens: bad args")
-    _refused(lib, f, ok, [dict(batch=0), dict(n=0), dict(dim=0), dict(dim=6), dict(dim=7), dict(tok=P16 + 4), dict(pos=P16 + 8), dict(out=P16 + 2)], "idb_embed_tokens: dims/alignment")
-    _refused(lib, f, ok, [dict(batch=1 << 13, n=1 << 13, dim=1 << 13), dict(batch=1 << 16, n=1 << 15, dim=4), dict(batch=2 ** 31 - 1, n=2 ** 31 - 1, dim=2 ** 31 - 4)],
+    MC.refused(lib, _pos(f), ok, MC.BAD_DTYPES + [dict(ids=None), dict(tok=None), dict(pos=None), dict(out=None)], "idb_embed_tokens: bad args")
+    MC.refused(lib, _pos(f), ok, [dict(batch=0), dict(n=0), dict(dim=0), dict(dim=6), dict(dim=7), dict(tok=P16 + 4), dict(pos=P16 + 8), dict(out=P16 + 2)], "idb_embed_tokens: dims/alignment")
+    MC.refused(lib, _pos(f), ok, [dict(batch=1 << 13, n=1 << 13, dim=1 << 13), dict(batch=1 << 16, n=1 << 15, dim=4), dict(batch=2 ** 31 - 1, n=2 ** 31 - 1, dim=2 ** 31 - 4)],
              "idb_embed_tokens: 2^39")

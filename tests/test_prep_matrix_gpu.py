@@ -35,49 +35,20 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import matrix_common as MC  # noqa: E402
 import prep_matrix as P  # noqa: E402
 from faceposegenerator_amd import _lib as L  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-G = P.GUARD
-IDB = {"f16": L.IDB_F16, "bf16": L.IDB_BF16}
-_WORST = {}             # kernel and dtype -> (worst err / bound, where)
+W = MC.Worst("prep matrix")
 _ROUNDING = {}          # kernel and dtype -> [elements rounded once, elements rounded through fp32] where the two differ
 _EXACT = {}             # kernel and dtype -> bit-equal cases
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _dev_bits(bits):
-    return _dev(np.ascontiguousarray(bits, np.uint16).view(np.int16))
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _judge(kernel, what, got, ref, bound):
-    res = P.check(got, ref, bound)
-    print(P.describe(what, res))
-    assert res[0], P.describe(what, res)
-    if kernel not in _WORST or res[1] > _WORST[kernel][0]:
-        _WORST[kernel] = (res[1], what)
-
-
-def _same(kernel, what, got, want, mask=None):
-    """Bit-equality of two integer arrays; names the first element that differs."""
-    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
-    assert got.shape == want.shape, f"{what}: {got.shape} against {want.shape}"
-    diff = np.flatnonzero((got != want) if mask is None else ((got != want) & np.asarray(mask).reshape(-1)))
-    assert diff.size == 0, f"{what}: {diff.size} elements differ, the first at {int(diff[0])}: {int(got[diff[0]]):#x}, expected {int(want[diff[0]]):#x}"
+def _exact(kernel, what, got, want, mask=None):
+    """MC.same_bits, counted per kernel for the summary."""
+    MC.same_bits(what, got, want, mask)
     _EXACT[kernel] = _EXACT.get(kernel, 0) + 1
 
 
@@ -93,41 +64,6 @@ def _member(kernel, what, bits, exact, dt):
     r[1] += n_twice
 
 
-class _Out:
-    """n elements of 8, 16 or 32 bits, pre-filled with a pattern (a NaN for 16 and 32 bits), between guards of the same pattern; `shift`
-    moves the destination that many elements past the 16-byte boundary (the skipped elements count as guard)."""
-
-    def __init__(self, n, bits=32, shift=0, pattern=None):
-        self.n, self.size, self.shift = n, bits // 8, shift
-        self.pattern = pattern if pattern is not None else (P.NAN32 if bits == 32 else P.NAN16)
-        dtype = {8: torch.uint8, 16: torch.int16, 32: torch.int32}[bits]
-        self.buf = torch.full((n + 2 * G + shift,), self.pattern, dtype=dtype, device=DEV)
-        assert (self.buf.data_ptr() + self.size * G) % 16 == 0
-        self.ptr = self.buf.data_ptr() + self.size * (G + shift)
-
-    def raw(self, what):
-        host = self.buf.cpu().numpy()
-        lo = G + self.shift
-        assert (host[:lo] == self.pattern).all() and (host[lo + self.n:] == self.pattern).all(), f"{what}: guard elements overwritten"
-        return host[lo:lo + self.n]
-
-    def f32(self, what):
-        return self.raw(what).view(np.float32)
-
-    def u32(self, what):
-        return self.raw(what).view(np.uint32)
-
-    def u16(self, what):
-        return self.raw(what).view(np.uint16)
-
-
-def _prefilled(values):
-    """An in-place fp32 buffer between guards: (tensor, pointer)."""
-    out = _Out(values.size)
-    out.buf[G:G + values.size] = _dev(values.reshape(-1).view(np.int32))
-    return out
-
-
 SHIFTS = (0, 1)
 
 
@@ -136,62 +72,62 @@ SHIFTS = (0, 1)
 @pytest.mark.parametrize("shape", P.PACK_CONV_SHAPES, ids=str)
 def test_pack_conv_weight(lib, shape, dt):
     cout, cin, taps = shape
-    src = _dev(P.pack_conv_input(shape))
+    src = MC.dev(P.pack_conv_input(shape))
     for shift in SHIFTS:
         what = f"idb_pack_conv_weight {shape} {dt} shift {shift}"
-        out = _Out(src.numel(), 16, shift)
-        L.check(lib.idb_pack_conv_weight(src.data_ptr(), out.ptr, cout, cin, taps, IDB[dt], _stream()), what)
+        out = MC.Guarded(src.numel(), 2, shift=shift)
+        L.check(lib.idb_pack_conv_weight(src.data_ptr(), out.ptr, cout, cin, taps, MC.IDB[dt], MC.stream()), what)
         torch.cuda.synchronize()
-        _same(f"idb_pack_conv_weight {dt}", what, out.u16(what), P.pack_conv_reference(shape, dt))
+        _exact(f"idb_pack_conv_weight {dt}", what, out.raw(what), P.pack_conv_reference(shape, dt))
 
 
 @pytest.mark.parametrize("dt", P.DTYPES)
 @pytest.mark.parametrize("shape", P.PACK_MATRIX_SHAPES, ids=str)
 def test_pack_matrix(lib, shape, dt):
     rows, cols, geglu = shape
-    src = _dev(P.matrix_inputs(shape)[0])
+    src = MC.dev(P.matrix_inputs(shape)[0])
     for shift in SHIFTS:
         what = f"idb_pack_matrix {shape} {dt} shift {shift}"
-        out = _Out(rows * cols, 16, shift)
-        L.check(lib.idb_pack_matrix(src.data_ptr(), out.ptr, rows, cols, geglu, IDB[dt], _stream()), what)
+        out = MC.Guarded(rows * cols, 2, shift=shift)
+        L.check(lib.idb_pack_matrix(src.data_ptr(), out.ptr, rows, cols, geglu, MC.IDB[dt], MC.stream()), what)
         torch.cuda.synchronize()
-        _same(f"idb_pack_matrix {dt}", what, out.u16(what), P.pack_matrix_reference(shape, dt))
+        _exact(f"idb_pack_matrix {dt}", what, out.raw(what), P.pack_matrix_reference(shape, dt))
 
 
 @pytest.mark.parametrize("dt", P.DTYPES)
 @pytest.mark.parametrize("shape", P.PACK_MATRIX_SHAPES, ids=str)
 def test_pack_matrix_scaled(lib, shape, dt):
     rows, cols, geglu = shape
-    src, cs = (_dev(v) for v in P.matrix_inputs(shape, dt))
+    src, cs = (MC.dev(v) for v in P.matrix_inputs(shape, dt))
     for shift in SHIFTS:
         what = f"idb_pack_matrix_scaled {shape} {dt} shift {shift}"
-        out = _Out(rows * cols, 16, shift)
-        L.check(lib.idb_pack_matrix_scaled(src.data_ptr(), out.ptr, rows, cols, geglu, cs.data_ptr(), IDB[dt], _stream()), what)
+        out = MC.Guarded(rows * cols, 2, shift=shift)
+        L.check(lib.idb_pack_matrix_scaled(src.data_ptr(), out.ptr, rows, cols, geglu, cs.data_ptr(), MC.IDB[dt], MC.stream()), what)
         torch.cuda.synchronize()
-        _member(f"idb_pack_matrix_scaled {dt}", what, out.u16(what), P.pack_scaled_exact(shape, dt), dt)
+        _member(f"idb_pack_matrix_scaled {dt}", what, out.raw(what), P.pack_scaled_exact(shape, dt), dt)
 
 
 @pytest.mark.parametrize("dt", P.DTYPES)
 @pytest.mark.parametrize("case", P.lora_cases(), ids=lambda c: c.name)
 def test_lora_merge(lib, case, dt):
     rows, cols, _ = case.shape
-    w, a, b, cs = (_dev(v) for v in P.lora_inputs(case, dt))
+    w, a, b, cs = (MC.dev(v) for v in P.lora_inputs(case, dt))
     pa, pb = (None, None) if case.rank0 else (a.data_ptr(), b.data_ptr())
     name = "idb_lora_merge_scaled" if case.scaled else "idb_lora_merge"
     for shift in SHIFTS:
         what = f"{name} {case.name} {dt} shift {shift}"
-        out = _Out(rows * cols, 16, shift)
+        out = MC.Guarded(rows * cols, 2, shift=shift)
         if case.scaled:
-            L.check(lib.idb_lora_merge_scaled(w.data_ptr(), pa, pb, out.ptr, rows, cols, case.rank, case.scale, cs.data_ptr(), IDB[dt], _stream()), what)
+            L.check(lib.idb_lora_merge_scaled(w.data_ptr(), pa, pb, out.ptr, rows, cols, case.rank, case.scale, cs.data_ptr(), MC.IDB[dt], MC.stream()), what)
         else:
-            L.check(lib.idb_lora_merge(w.data_ptr(), pa, pb, out.ptr, rows, cols, case.rank, case.scale, IDB[dt], _stream()), what)
+            L.check(lib.idb_lora_merge(w.data_ptr(), pa, pb, out.ptr, rows, cols, case.rank, case.scale, MC.IDB[dt], MC.stream()), what)
         torch.cuda.synchronize()
-        bits = out.u16(what)
+        bits = out.raw(what)
         if case.rank0:
             _member(f"{name} rank 0 {dt}", what, bits, P.lora_exact(case, dt), dt)
         else:
             ref, bound = P.lora_reference(case, dt)
-            _judge(f"{name} {dt}", what, P.from_bits(bits, dt).reshape(ref.shape), ref, bound)
+            W.judge(f"{name} {dt}", what, P.from_bits(bits, dt).reshape(ref.shape), ref, bound)
 
 
 @pytest.mark.parametrize("dt", P.DTYPES)
@@ -200,14 +136,14 @@ def test_lora_merge_scaled_by_one_is_pack_matrix(lib, shape, dt):
     """rank 0 and a column scale of exactly 1: the product is exact, the output is idb_pack_matrix's bit for bit."""
     rows, cols, _ = shape
     what = f"idb_lora_merge_scaled {shape} {dt} rank 0, col_scale 1"
-    w = _dev(P.lora_inputs(P.LoraCase(shape, 0.5, True, True))[0])
-    ones = torch.ones(cols, dtype=torch.float32, device=DEV)
-    merged, packed = _Out(rows * cols, 16), _Out(rows * cols, 16)
-    L.check(lib.idb_lora_merge_scaled(w.data_ptr(), None, None, merged.ptr, rows, cols, 0, -1.75, ones.data_ptr(), IDB[dt], _stream()), what)
-    L.check(lib.idb_pack_matrix(w.data_ptr(), packed.ptr, rows, cols, 0, IDB[dt], _stream()), what)
+    w = MC.dev(P.lora_inputs(P.LoraCase(shape, 0.5, True, True))[0])
+    ones = torch.ones(cols, dtype=torch.float32, device=MC.DEV)
+    merged, packed = MC.Guarded(rows * cols, 2), MC.Guarded(rows * cols, 2)
+    L.check(lib.idb_lora_merge_scaled(w.data_ptr(), None, None, merged.ptr, rows, cols, 0, -1.75, ones.data_ptr(), MC.IDB[dt], MC.stream()), what)
+    L.check(lib.idb_pack_matrix(w.data_ptr(), packed.ptr, rows, cols, 0, MC.IDB[dt], MC.stream()), what)
     torch.cuda.synchronize()
-    _same(f"idb_lora_merge_scaled rank 0 {dt}", what, merged.u16(what), packed.u16(what))
-    _same(f"idb_lora_merge_scaled rank 0 {dt}", what, merged.u16(what), P.to_bits(w.cpu().numpy(), dt))
+    _exact(f"idb_lora_merge_scaled rank 0 {dt}", what, merged.raw(what), packed.raw(what))
+    _exact(f"idb_lora_merge_scaled rank 0 {dt}", what, merged.raw(what), P.to_bits(w.cpu().numpy(), dt))
 
 
 @pytest.mark.parametrize("dt", P.DTYPES)
@@ -215,13 +151,13 @@ def test_lora_merge_scaled_by_one_is_pack_matrix(lib, shape, dt):
 def test_tile_weight(lib, shape, dt):
     n, k = shape
     what = f"idb_tile_weight {shape} {dt}"
-    src = _dev_bits(P.tile_input(shape))
+    src = MC.dev(P.tile_input(shape), np.uint16)
     need = lib.idb_tiled_weight_bytes(n, k)
     assert need == P.tiled_bytes(n, k) and src.data_ptr() % 16 == 0
-    out = _Out(need // 2, 16)
-    L.check(lib.idb_tile_weight(src.data_ptr(), out.ptr, n, k, IDB[dt], _stream()), what)
+    out = MC.Guarded(need // 2, 2)
+    L.check(lib.idb_tile_weight(src.data_ptr(), out.ptr, n, k, MC.IDB[dt], MC.stream()), what)
     torch.cuda.synchronize()
-    _same(f"idb_tile_weight {dt}", what, out.u16(what), P.tile_reference(shape))
+    _exact(f"idb_tile_weight {dt}", what, out.raw(what), P.tile_reference(shape))
 
 
 @pytest.mark.parametrize("dt", P.DTYPES)
@@ -229,30 +165,30 @@ def test_tile_weight(lib, shape, dt):
 def test_ln_fold_vectors(lib, case, dt):
     what = f"idb_ln_fold_vectors {case.name} {dt}"
     w, a, b, wq, beta, bias = P.fold_inputs(case, dt)
-    dw, dbeta, dbias, dwq = _dev(w), _dev(beta), _dev(bias), _dev_bits(P.to_bits(wq, dt))
-    da, db = (_dev(a), _dev(b)) if case.rank else (None, None)
-    u, v = _Out(case.rows), _Out(case.rows)
-    L.check(lib.idb_ln_fold_vectors(dw.data_ptr(), None if case.null_a else _ptr(da), _ptr(db), case.rank, P.FOLD_SCALE, dwq.data_ptr(), dbeta.data_ptr(),
-                                    dbias.data_ptr() if case.bias else None, u.ptr, v.ptr, case.rows, case.cols, case.geglu, IDB[dt], _stream()), what)
+    dw, dbeta, dbias, dwq = MC.dev(w), MC.dev(beta), MC.dev(bias), MC.dev(P.to_bits(wq, dt))
+    da, db = (MC.dev(a), MC.dev(b)) if case.rank else (None, None)
+    u, v = MC.Guarded(case.rows), MC.Guarded(case.rows)
+    L.check(lib.idb_ln_fold_vectors(dw.data_ptr(), None if case.null_a else MC.ptr(da), MC.ptr(db), case.rank, P.FOLD_SCALE, dwq.data_ptr(), dbeta.data_ptr(),
+                                    dbias.data_ptr() if case.bias else None, u.ptr, v.ptr, case.rows, case.cols, case.geglu, MC.IDB[dt], MC.stream()), what)
     torch.cuda.synchronize()
     ru, bu, rv, bv = P.fold_reference(case, dt)
-    _judge(f"idb_ln_fold_vectors u {dt}", what + " u", u.f32(what), ru, bu)
-    _judge(f"idb_ln_fold_vectors v {dt}", what + " v", v.f32(what), rv, bv)
+    W.judge(f"idb_ln_fold_vectors u {dt}", what + " u", u.f32(what), ru, bu)
+    W.judge(f"idb_ln_fold_vectors v {dt}", what + " v", v.f32(what), rv, bv)
 
 
 # ---- the API boundary ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dt", P.DTYPES)
 @pytest.mark.parametrize("count", P.CAST_COUNTS)
 def test_cast_f32(lib, count, dt):
-    x = _dev(P.cast_input(count))
+    x = MC.dev(P.cast_input(count))
     want, mask = P.cast_reference(count, dt)
     for shift, fill in ((0, P.NAN16), (1, P.NAN16), (0, 0x3C00)):           # 0x3C00 is no NaN in either dtype: an unwritten NaN element shows
         what = f"idb_cast_f32 {count} {dt} shift {shift} prefill {fill:#x}"
-        out = _Out(count, 16, shift, pattern=fill)
-        L.check(lib.idb_cast_f32(x.data_ptr(), out.ptr, count, IDB[dt], _stream()), what)
+        out = MC.Guarded(count, 2, pattern=fill, shift=shift)
+        L.check(lib.idb_cast_f32(x.data_ptr(), out.ptr, count, MC.IDB[dt], MC.stream()), what)
         torch.cuda.synchronize()
-        bits = out.u16(what)
-        _same(f"idb_cast_f32 {dt}", what, bits, want, mask)
+        bits = out.raw(what)
+        _exact(f"idb_cast_f32 {dt}", what, bits, want, mask)
         nan = np.isnan(P.from_bits(bits, dt))
         assert np.array_equal(nan, ~mask), f"{what}: a NaN input must give a NaN, and nothing else may (elements {np.flatnonzero(nan != ~mask)[:4]})"
 
@@ -264,14 +200,14 @@ def test_nhwc_to_nchw(lib, shape, dt):
     name = "idb_f32_nhwc_to_nchw" if dt == "f32" else "idb_nhwc_to_nchw_f32"
     what = f"{name} {shape} {dt}"
     x = P.transpose_input(shape, dt)
-    dx = _dev(x) if dt == "f32" else _dev_bits(x)
-    out = _Out(x.size)
+    dx = MC.dev(x) if dt == "f32" else MC.dev(x, np.uint16)
+    out = MC.Guarded(x.size)
     if dt == "f32":
-        L.check(lib.idb_f32_nhwc_to_nchw(dx.data_ptr(), out.ptr, b, hw, c, _stream()), what)
+        L.check(lib.idb_f32_nhwc_to_nchw(dx.data_ptr(), out.ptr, b, hw, c, MC.stream()), what)
     else:
-        L.check(lib.idb_nhwc_to_nchw_f32(dx.data_ptr(), out.ptr, b, hw, c, IDB[dt], _stream()), what)
+        L.check(lib.idb_nhwc_to_nchw_f32(dx.data_ptr(), out.ptr, b, hw, c, MC.IDB[dt], MC.stream()), what)
     torch.cuda.synchronize()
-    _same(f"{name} {dt}", what, out.u32(what), P.transpose_reference(shape, dt).view(np.uint32))
+    _exact(f"{name} {dt}", what, out.raw(what), P.transpose_reference(shape, dt).view(np.uint32))
 
 
 @pytest.mark.parametrize("dt", P.DTYPES)
@@ -281,30 +217,30 @@ def test_embed_tokens(lib, shape, dt):
     what = f"idb_embed_tokens {shape} {dt}"
     ids, tok, pos = P.embed_inputs(shape, dt)
     assert ids.min() >= 0 and ids.max() < vocab
-    dids, dtok, dpos = _dev(ids), _dev(tok), _dev(pos)
+    dids, dtok, dpos = MC.dev(ids), MC.dev(tok), MC.dev(pos)
     assert dtok.data_ptr() % 16 == 0 and dpos.data_ptr() % 16 == 0
-    out = _Out(ids.size * dim, 16)
-    L.check(lib.idb_embed_tokens(dids.data_ptr(), dtok.data_ptr(), dpos.data_ptr(), out.ptr, batch, n_tokens, dim, IDB[dt], _stream()), what)
+    out = MC.Guarded(ids.size * dim, 2)
+    L.check(lib.idb_embed_tokens(dids.data_ptr(), dtok.data_ptr(), dpos.data_ptr(), out.ptr, batch, n_tokens, dim, MC.IDB[dt], MC.stream()), what)
     torch.cuda.synchronize()
-    _member(f"idb_embed_tokens {dt}", what, out.u16(what), P.embed_exact(shape, dt), dt)
+    _member(f"idb_embed_tokens {dt}", what, out.raw(what), P.embed_exact(shape, dt), dt)
 
 
 @pytest.mark.parametrize("outputs", ("both", "u8_only", "img_only"))
 @pytest.mark.parametrize("name", list(P.POST_CASES))
 def test_postprocess(lib, name, outputs):
     x = P.POST_CASES[name]()
-    dx = _dev(x)
+    dx = MC.dev(x)
     ref_v, ref_u8 = P.post_reference(name)
     for fill in (0xA5, 0x5A):
         what = f"idb_postprocess {name} {outputs} prefill {fill:#x}"
-        img = _Out(x.size) if outputs != "u8_only" else None
-        u8 = _Out(x.size, 8, pattern=fill) if outputs != "img_only" else None
-        L.check(lib.idb_postprocess(dx.data_ptr(), img.ptr if img else None, u8.ptr if u8 else None, x.size, _stream()), what)
+        img = MC.Guarded(x.size) if outputs != "u8_only" else None
+        u8 = MC.Guarded(x.size, 1, pattern=fill) if outputs != "img_only" else None
+        L.check(lib.idb_postprocess(dx.data_ptr(), img.ptr if img else None, u8.ptr if u8 else None, x.size, MC.stream()), what)
         torch.cuda.synchronize()
         if img:
-            _same("idb_postprocess img01", what + " img01", img.u32(what), ref_v.view(np.uint32))
+            _exact("idb_postprocess img01", what + " img01", img.raw(what), ref_v.view(np.uint32))
         if u8:
-            _same("idb_postprocess u8", what + " u8", u8.raw(what), ref_u8)
+            _exact("idb_postprocess u8", what + " u8", u8.raw(what), ref_u8)
 
 
 # ---- the latent path -----------------------------------------------------------------------------------------------------------------
@@ -315,18 +251,18 @@ def test_vae_sample(lib, shape, mode):
     what = f"idb_vae_sample {shape} {mode}"
     with_noise = mode.startswith("noise")
     moments, noise = P.vae_inputs(shape)
-    dm, dn = _dev(moments), (_dev(noise) if with_noise else None)
-    lat = _Out(b * c * hw)
-    mean = _Out(b * c * hw) if mode.endswith(("all", "mean_only")) else None
-    lv = _Out(b * c * hw) if mode.endswith(("all", "logvar_only")) else None
-    L.check(lib.idb_vae_sample(dm.data_ptr(), _ptr(dn), P.VAE_SCALE, lat.ptr, mean.ptr if mean else None, lv.ptr if lv else None, b, c, hw, _stream()), what)
+    dm, dn = MC.dev(moments), (MC.dev(noise) if with_noise else None)
+    lat = MC.Guarded(b * c * hw)
+    mean = MC.Guarded(b * c * hw) if mode.endswith(("all", "mean_only")) else None
+    lv = MC.Guarded(b * c * hw) if mode.endswith(("all", "logvar_only")) else None
+    L.check(lib.idb_vae_sample(dm.data_ptr(), MC.ptr(dn), P.VAE_SCALE, lat.ptr, mean.ptr if mean else None, lv.ptr if lv else None, b, c, hw, MC.stream()), what)
     torch.cuda.synchronize()
     ref, bound, rmean, rlv = P.vae_reference(shape, with_noise)
-    _judge("idb_vae_sample" + ("" if with_noise else " mode"), what, lat.f32(what).reshape(ref.shape), ref, bound)
+    W.judge("idb_vae_sample" + ("" if with_noise else " mode"), what, lat.f32(what).reshape(ref.shape), ref, bound)
     if mean:
-        _same("idb_vae_sample mean", what + " mean", mean.u32(what), rmean.view(np.uint32))
+        _exact("idb_vae_sample mean", what + " mean", mean.raw(what), rmean.view(np.uint32))
     if lv:
-        _same("idb_vae_sample logvar", what + " logvar", lv.u32(what), rlv.view(np.uint32))
+        _exact("idb_vae_sample logvar", what + " logvar", lv.raw(what), rlv.view(np.uint32))
 
 
 @pytest.mark.parametrize("case", P.cfg_cases(), ids=lambda c: c.name)
@@ -334,21 +270,20 @@ def test_cfg_ddpm_step(lib, case):
     what = f"idb_cfg_ddpm_step {case.name}"
     b, c, hw = case.shape
     eps, lat, noise = P.cfg_inputs(case.shape)
-    deps = _dev(eps if case.cfg else eps[:b])                               # without guidance the kernel is handed the one half only
-    dnoise, dcoef = (_dev(noise) if case.noise else None), _dev(case.coef)
-    latents = _prefilled(lat)
-    x0 = _Out(lat.size) if case.x0 else None
-    L.check(lib.idb_cfg_ddpm_step(deps.data_ptr(), latents.ptr, _ptr(dnoise), dcoef.data_ptr(), x0.ptr if x0 else None, b, c, hw, case.cfg, case.vpred, _stream()), what)
+    deps = MC.dev(eps if case.cfg else eps[:b])                               # without guidance the kernel is handed the one half only
+    dnoise, dcoef = (MC.dev(noise) if case.noise else None), MC.dev(case.coef)
+    latents = MC.Guarded(lat.size, init=lat)
+    x0 = MC.Guarded(lat.size) if case.x0 else None
+    L.check(lib.idb_cfg_ddpm_step(deps.data_ptr(), latents.ptr, MC.ptr(dnoise), dcoef.data_ptr(), x0.ptr if x0 else None, b, c, hw, case.cfg, case.vpred, MC.stream()), what)
     torch.cuda.synchronize()
     prev, bp, r0, b0 = P.cfg_reference(case)
-    _judge("idb_cfg_ddpm_step latents", what + " latents", latents.f32(what).reshape(prev.shape), prev, bp)
+    W.judge("idb_cfg_ddpm_step latents", what + " latents", latents.f32(what).reshape(prev.shape), prev, bp)
     if x0:
-        _judge("idb_cfg_ddpm_step x0", what + " x0", x0.f32(what).reshape(r0.shape), r0, b0)
+        W.judge("idb_cfg_ddpm_step x0", what + " x0", x0.f32(what).reshape(r0.shape), r0, b0)
 
 
 def test_summary():
-    for k in sorted(_WORST):
-        print(f"prep matrix: {k}: worst err / bound {_WORST[k][0]:.4f} ({_WORST[k][1]})")
+    W.show()
     for k in sorted(_EXACT):
         print(f"prep matrix: {k}: bit-equal in {_EXACT[k]} comparisons")
     for k in sorted(_ROUNDING):

@@ -14,15 +14,12 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import matrix_common as MC  # noqa: E402
 import stem_matrix as S  # noqa: E402
 
 T64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64))   # noqa: E731
 STEMS = [(k, s, e, dt) for k, shapes in (("arcface", S.ASTEM_SHAPES), ("pose", S.PSTEM_SHAPES)) for s in shapes for e in S.ENTRIES for dt in S.DTYPES]
-_WORST = {}
-
-
-def _note(kernel, ratio):
-    _WORST[kernel] = max(_WORST.get(kernel, 0.0), ratio)
+W = MC.Worst("stem matrix, fp32 emulation")
 
 
 # ---- number formats ------------------------------------------------------------------------------------------------------------------
@@ -247,7 +244,7 @@ def test_stem_emulation_passes(kind, shape, entry, dt):
     out, out2 = S.emulate_stem(kind, shape, entry, dt)
     res = S.check(out, ref, bound)
     assert res[0], S.describe(f"{kind} stem {shape} {entry} {dt}", res)
-    _note(f"idb_{kind}_stem {dt}", res[1])
+    W.note(f"idb_{kind}_stem {dt}", res[1])
     if kind == "arcface":
         _, _, _, s2, b2 = S.stem_params(kind)
         assert np.array_equal(out2, S.out2_of(out, s2, b2, dt)) and np.array_equal(S.round_T(out2, dt), out2)
@@ -259,7 +256,7 @@ def test_conv_in_emulation_passes(case):
         ref, bound = S.conv_in_reference(case, dt, e_scale=0.5)                   # half the fp32 allowance, the whole rounding to T
         res = S.check(S.emulate_conv_in(case, dt), ref, bound)
         assert res[0], S.describe(f"{case.name} {dt}", res)
-        _note(f"idb_conv_in {dt}", res[1])
+        W.note(f"idb_conv_in {dt}", res[1])
 
 
 @pytest.mark.parametrize("case", S.linear_cases(), ids=lambda c: c.name)
@@ -267,7 +264,7 @@ def test_linear_emulation_passes(case):
     ref, bound = S.linear_reference(case)
     res = S.check(S.emulate_linear(case), ref, bound)
     assert res[0] and res[1] <= 0.5, S.describe(case.name, res)
-    _note("idb_linear_f32", res[1])
+    W.note("idb_linear_f32", res[1])
 
 
 @pytest.mark.parametrize("case", S.head_cases(), ids=lambda c: c.name)
@@ -276,7 +273,7 @@ def test_head_emulation_passes(case):
         ref, bound = S.head_reference(case, dt)
         res = S.check(S.emulate_head(case, dt), ref, bound)
         assert res[0] and res[1] <= 0.5, S.describe(f"{case.name} {dt}", res)
-        _note(f"idb_arcface_head {dt}", res[1])
+        W.note(f"idb_arcface_head {dt}", res[1])
 
 
 @pytest.mark.parametrize("shape", S.PHEAD_SHAPES, ids=str)
@@ -286,7 +283,7 @@ def test_pose_head_emulation_passes(shape):
         r, a = S.emulate_phead(shape, dt)
         for name, res in (("R", S.check(r, rot, tol_r)), ("angles", S.check(a, ang, tol_a))):
             assert res[0] and res[1] <= 0.5, S.describe(f"pose head {shape} {dt} {name}", res)
-            _note(f"idb_pose_head {name} {dt}", res[1])
+            W.note(f"idb_pose_head {name} {dt}", res[1])
 
 
 @pytest.mark.parametrize("n,dim", S.SIN_SHAPES)
@@ -294,91 +291,70 @@ def test_sinusoid_emulation_passes(n, dim):
     ref, bar, _ = S.sin_bound(n, dim)
     res = S.check(S.emulate_sin(n, dim), ref, bar)
     assert res[0] and res[1] <= 0.5, S.describe(f"sinusoid {n} x {dim}", res)
-    _note("idb_timestep_sinusoid", res[1])
+    W.note("idb_timestep_sinusoid", res[1])
 
 
 def test_summary():
-    for k in sorted(_WORST):
-        print(f"stem matrix, fp32 emulation: {k}: worst err / bound {_WORST[k]:.4f}")
+    W.show()
 
 
 # ---- argument checks: every IDB_REQUIRE of the seven entry points answers before any HIP call -----------------------------------------
-P = 1 << 20              # any non-null 16-byte-aligned address: none of these calls dereferences it
-EINVAL = -1
+P = MC.P16
 
 
-@pytest.fixture(scope="module")
-def dts():
-    from faceposegenerator_amd import _lib
-    return _lib.IDB_F16, _lib.IDB_BF16
+def test_arcface_stem_argument_checks(lib):
+    ok = dict(x=P, u8=1, batch=2, h=7, w=33, wt=P, bias=P, slope=P, s2=P, b2=P, out=P, out2=P, dtype=MC.IDB["f16"])
+    call = lambda a: lib.idb_arcface_stem(a["x"], a["u8"], a["batch"], a["h"], a["w"], a["wt"], a["bias"], a["slope"], a["s2"], a["b2"],   # noqa: E731
+                                          a["out"], a["out2"], a["dtype"], None)
+    MC.refused(lib, call, ok, MC.BAD_DTYPES, "idb_arcface_stem: dtype")
+    MC.refused(lib, call, ok, [dict(x=None), dict(wt=None), dict(bias=None), dict(slope=None), dict(out=None), dict(out=P + 8), dict(out2=P + 2)],
+               "idb_arcface_stem: null or unaligned")
+    MC.refused(lib, call, ok, [dict(s2=None), dict(b2=None), dict(s2=None, b2=None)], "idb_arcface_stem: out2 needs")
+    MC.refused(lib, call, ok, [dict(w=257), dict(w=0), dict(h=0), dict(batch=0), dict(batch=65536), dict(batch=-1)], "idb_arcface_stem: batch 1..65535")
 
 
-def _all_refused(lib, call, variants, text):
-    before = lib.idb_launch_count()
-    for kw in variants:
-        rc = call(**kw)
-        msg = lib.idb_last_error()
-        assert rc == EINVAL and text.encode() in msg, (kw, rc, msg)
-    assert lib.idb_launch_count() == before
+def test_pose_stem_argument_checks(lib):
+    ok = dict(x=P, u8=1, batch=2, h=4, w=6, wt=P, bias=P, out=P, dtype=MC.IDB["bf16"])
+    call = lambda a: lib.idb_pose_stem(a["x"], a["u8"], a["batch"], a["h"], a["w"], a["wt"], a["bias"], a["out"], a["dtype"], None)   # noqa: E731
+    MC.refused(lib, call, ok, MC.BAD_DTYPES, "idb_pose_stem: dtype")
+    MC.refused(lib, call, ok, [dict(x=None), dict(wt=None), dict(bias=None), dict(out=None), dict(out=P + 4)], "idb_pose_stem: null or unaligned")
+    MC.refused(lib, call, ok, [dict(w=513), dict(w=0), dict(h=0), dict(batch=0), dict(batch=65536)], "idb_pose_stem: batch 1..65535")
 
 
-def _bad_dtypes(dts):
-    return [dict(dtype=d) for d in (-1, 99, max(dts) + 1) if d not in dts]
-
-
-def test_arcface_stem_argument_checks(lib, dts):
-    ok = dict(x=P, u8=1, batch=2, h=7, w=33, wt=P, bias=P, slope=P, s2=P, b2=P, out=P, out2=P, dtype=dts[0])
-    call = lambda **kw: (lambda a: lib.idb_arcface_stem(a["x"], a["u8"], a["batch"], a["h"], a["w"], a["wt"], a["bias"], a["slope"], a["s2"], a["b2"],   # noqa: E731
-                                                        a["out"], a["out2"], a["dtype"], None))({**ok, **kw})
-    _all_refused(lib, call, _bad_dtypes(dts), "idb_arcface_stem: dtype")
-    _all_refused(lib, call, [dict(x=None), dict(wt=None), dict(bias=None), dict(slope=None), dict(out=None), dict(out=P + 8), dict(out2=P + 2)],
-                 "idb_arcface_stem: null or unaligned")
-    _all_refused(lib, call, [dict(s2=None), dict(b2=None), dict(s2=None, b2=None)], "idb_arcface_stem: out2 needs")
-    _all_refused(lib, call, [dict(w=257), dict(w=0), dict(h=0), dict(batch=0), dict(batch=65536), dict(batch=-1)], "idb_arcface_stem: batch 1..65535")
-
-
-def test_pose_stem_argument_checks(lib, dts):
-    ok = dict(x=P, u8=1, batch=2, h=4, w=6, wt=P, bias=P, out=P, dtype=dts[1])
-    call = lambda **kw: (lambda a: lib.idb_pose_stem(a["x"], a["u8"], a["batch"], a["h"], a["w"], a["wt"], a["bias"], a["out"], a["dtype"], None))({**ok, **kw})   # noqa: E731
-    _all_refused(lib, call, _bad_dtypes(dts), "idb_pose_stem: dtype")
-    _all_refused(lib, call, [dict(x=None), dict(wt=None), dict(bias=None), dict(out=None), dict(out=P + 4)], "idb_pose_stem: null or unaligned")
-    _all_refused(lib, call, [dict(w=513), dict(w=0), dict(h=0), dict(batch=0), dict(batch=65536)], "idb_pose_stem: batch 1..65535")
-
-
-def test_conv_in_argument_checks(lib, dts):
-    ok = dict(x=P, wt=P, bias=P, out=P, batch=2, rep=2, cin=4, h=9, w=31, cout=16, pw=P, pb=P, dtype=dts[0])
-    call = lambda **kw: (lambda a: lib.idb_conv_in(a["x"], a["wt"], a["bias"], a["out"], a["batch"], a["rep"], a["cin"], a["h"], a["w"], a["cout"], 1.0,   # noqa: E731
-                                                   a["pw"], a["pb"], a["dtype"], None))({**ok, **kw})
-    _all_refused(lib, call, _bad_dtypes(dts), "idb_conv_in: dtype")
-    _all_refused(lib, call, [dict(x=None), dict(wt=None), dict(bias=None), dict(out=None), dict(out=P + 2)], "idb_conv_in: null/unaligned")
-    _all_refused(lib, call, [dict(cin=5), dict(cin=0), dict(cout=12), dict(cout=0), dict(batch=0), dict(rep=0), dict(h=0), dict(w=0)],
-                 "idb_conv_in: unsupported dims")
-    _all_refused(lib, call, [dict(pb=None), dict(pw=None)], "idb_conv_in: pre_w/pre_b")
+def test_conv_in_argument_checks(lib):
+    ok = dict(x=P, wt=P, bias=P, out=P, batch=2, rep=2, cin=4, h=9, w=31, cout=16, pw=P, pb=P, dtype=MC.IDB["f16"])
+    call = lambda a: lib.idb_conv_in(a["x"], a["wt"], a["bias"], a["out"], a["batch"], a["rep"], a["cin"], a["h"], a["w"], a["cout"], 1.0,   # noqa: E731
+                                     a["pw"], a["pb"], a["dtype"], None)
+    MC.refused(lib, call, ok, MC.BAD_DTYPES, "idb_conv_in: dtype")
+    MC.refused(lib, call, ok, [dict(x=None), dict(wt=None), dict(bias=None), dict(out=None), dict(out=P + 2)], "idb_conv_in: null/unaligned")
+    MC.refused(lib, call, ok, [dict(cin=5), dict(cin=0), dict(cout=12), dict(cout=0), dict(batch=0), dict(rep=0), dict(h=0), dict(w=0)],
+               "idb_conv_in: unsupported dims")
+    MC.refused(lib, call, ok, [dict(pb=None), dict(pw=None)], "idb_conv_in: pre_w/pre_b")
 
 
 def test_linear_and_sinusoid_argument_checks(lib):
-    f = lib.idb_linear_f32
-    call = lambda x=P, w=P, y=P, m=9, n=5, k=65: f(x, w, None, y, m, n, k, 0, None)   # noqa: E731
-    _all_refused(lib, call, [dict(x=None), dict(w=None), dict(y=None), dict(m=0), dict(n=0), dict(k=0), dict(m=-1)], "idb_linear_f32: bad args")
-    g = lib.idb_timestep_sinusoid
-    call = lambda t=P, out=P, n=5, dim=6: g(t, out, n, dim, None)   # noqa: E731
-    _all_refused(lib, call, [dict(dim=7), dict(dim=1), dict(dim=0), dict(n=0), dict(t=None), dict(out=None)], "idb_timestep_sinusoid: bad args")
+    ok = dict(x=P, w=P, y=P, m=9, n=5, k=65)
+    call = lambda a: lib.idb_linear_f32(a["x"], a["w"], None, a["y"], a["m"], a["n"], a["k"], 0, None)   # noqa: E731
+    MC.refused(lib, call, ok, [dict(x=None), dict(w=None), dict(y=None), dict(m=0), dict(n=0), dict(k=0), dict(m=-1)], "idb_linear_f32: bad args")
+    ok = dict(t=P, out=P, n=5, dim=6)
+    call = lambda a: lib.idb_timestep_sinusoid(a["t"], a["out"], a["n"], a["dim"], None)   # noqa: E731
+    MC.refused(lib, call, ok, [dict(dim=7), dict(dim=1), dict(dim=0), dict(n=0), dict(t=None), dict(out=None)], "idb_timestep_sinusoid: bad args")
 
 
-def test_arcface_head_argument_checks(lib, dts):
+def test_arcface_head_argument_checks(lib):
     need = S.head_workspace_bytes(3, 64, 544)
-    ok = dict(x=P, wt=P, y=P, m=3, n=64, k=544, dtype=dts[0], ws=P, nbytes=need)
-    call = lambda **kw: (lambda a: lib.idb_arcface_head(a["x"], a["wt"], None, a["y"], a["m"], a["n"], a["k"], a["dtype"], a["ws"], a["nbytes"], None))({**ok, **kw})   # noqa: E731
-    _all_refused(lib, call, _bad_dtypes(dts), "idb_arcface_head: dtype")
-    _all_refused(lib, call, [dict(n=96), dict(n=63), dict(k=560), dict(k=31), dict(m=0), dict(n=0), dict(k=0), dict(x=None), dict(wt=None), dict(y=None)],
-                 "idb_arcface_head: n % 64 == 0 and k % 32 == 0")
-    _all_refused(lib, call, [dict(nbytes=need - 1), dict(nbytes=0), dict(ws=None), dict(ws=P + 4)], "idb_arcface_head: workspace too small")
+    ok = dict(x=P, wt=P, y=P, m=3, n=64, k=544, dtype=MC.IDB["f16"], ws=P, nbytes=need)
+    call = lambda a: lib.idb_arcface_head(a["x"], a["wt"], None, a["y"], a["m"], a["n"], a["k"], a["dtype"], a["ws"], a["nbytes"], None)   # noqa: E731
+    MC.refused(lib, call, ok, MC.BAD_DTYPES, "idb_arcface_head: dtype")
+    MC.refused(lib, call, ok, [dict(n=96), dict(n=63), dict(k=560), dict(k=31), dict(m=0), dict(n=0), dict(k=0), dict(x=None), dict(wt=None), dict(y=None)],
+               "idb_arcface_head: n % 64 == 0 and k % 32 == 0")
+    MC.refused(lib, call, ok, [dict(nbytes=need - 1), dict(nbytes=0), dict(ws=None), dict(ws=P + 4)], "idb_arcface_head: workspace too small")
     assert lib.idb_arcface_head_workspace_bytes(3, 96, 544) == 0 and lib.idb_arcface_head_workspace_bytes(3, 64, 560) == 0
 
 
-def test_pose_head_argument_checks(lib, dts):
-    ok = dict(x=P, batch=2, hw=7, c=64, wt=P, bias=P, rot=P, ang=P, dtype=dts[1])
-    call = lambda **kw: (lambda a: lib.idb_pose_head(a["x"], a["batch"], a["hw"], a["c"], a["wt"], a["bias"], a["rot"], a["ang"], a["dtype"], None))({**ok, **kw})   # noqa: E731
-    _all_refused(lib, call, _bad_dtypes(dts), "idb_pose_head: dtype")
-    _all_refused(lib, call, [dict(x=None), dict(x=P + 8), dict(wt=None), dict(bias=None), dict(rot=None), dict(ang=None)], "idb_pose_head: null or unaligned")
-    _all_refused(lib, call, [dict(c=12), dict(c=4), dict(c=0), dict(hw=0), dict(batch=0)], "idb_pose_head: batch > 0")
+def test_pose_head_argument_checks(lib):
+    ok = dict(x=P, batch=2, hw=7, c=64, wt=P, bias=P, rot=P, ang=P, dtype=MC.IDB["bf16"])
+    call = lambda a: lib.idb_pose_head(a["x"], a["batch"], a["hw"], a["c"], a["wt"], a["bias"], a["rot"], a["ang"], a["dtype"], None)   # noqa: E731
+    MC.refused(lib, call, ok, MC.BAD_DTYPES, "idb_pose_head: dtype")
+    MC.refused(lib, call, ok, [dict(x=None), dict(x=P + 8), dict(wt=None), dict(bias=None), dict(rot=None), dict(ang=None)], "idb_pose_head: null or unaligned")
+    MC.refused(lib, call, ok, [dict(c=12), dict(c=4), dict(c=0), dict(hw=0), dict(batch=0)], "idb_pose_head: batch > 0")

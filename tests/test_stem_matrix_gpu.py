@@ -28,71 +28,16 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import matrix_common as MC  # noqa: E402
 import stem_matrix as S  # noqa: E402
 from faceposegenerator_amd import _lib as L  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-G = S.GUARD
-IDB = {"f16": L.IDB_F16, "bf16": L.IDB_BF16}
-_WORST = {}             # kernel and dtype -> (worst err / bound, where)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _dev_T(v32, dt):
-    """fp32 values of T -> a device tensor of their 16-bit patterns."""
-    return _dev(S.to_bits(v32, dt).view(np.int16).reshape(np.shape(v32)))
-
-
-def _note(kernel, res, where):
-    if kernel not in _WORST or res[1] > _WORST[kernel][0]:
-        _WORST[kernel] = (res[1], where)
-
-
-def _judge(kernel, what, got, ref, bound):
-    res = S.check(got, ref, bound)
-    print(S.describe(what, res))
-    assert res[0], S.describe(what, res)
-    _note(kernel, res, what)
-
-
-class _Out:
-    """n elements of 16 or 32 bits, pre-filled with the NaN pattern, between guards of the same pattern."""
-
-    def __init__(self, n, bits=32):
-        self.n, self.size = n, bits // 8
-        self.pattern = S.NAN32 if bits == 32 else S.NAN16
-        self.buf = torch.full((n + 2 * G,), self.pattern, dtype=torch.int32 if bits == 32 else torch.int16, device=DEV)
-        self.ptr = self.buf.data_ptr() + self.size * G
-        assert self.ptr % 16 == 0
-
-    def raw(self, what):
-        host = self.buf.cpu().numpy()
-        assert (host[:G] == self.pattern).all() and (host[G + self.n:] == self.pattern).all(), f"{what}: guard elements overwritten"
-        return host[G:G + self.n]
-
-    def f32(self, what):
-        return self.raw(what).view(np.float32)
-
-    def T(self, what, dt):
-        """(fp32 values, 16-bit patterns)."""
-        bits = self.raw(what).view(np.uint16)
-        return S.from_bits(bits, dt), bits
+W = MC.Worst("stem matrix")
 
 
 # ---- the stems -----------------------------------------------------------------------------------------------------------------------
-def _stem_input(kind, shape, entry):
-    return _dev(S.stem_raw(kind, shape, entry))
-
-
 @pytest.mark.parametrize("dt", S.DTYPES)
 @pytest.mark.parametrize("entry", S.ENTRIES)
 @pytest.mark.parametrize("shape", S.ASTEM_SHAPES, ids=str)
@@ -100,17 +45,17 @@ def test_arcface_stem(lib, shape, entry, dt):
     what = f"idb_arcface_stem {shape} {entry} {dt}"
     b, h, w = shape
     wt, bias, slope, s2, b2 = S.stem_params("arcface")
-    x, dw, db, dsl, ds2, db2 = _stem_input("arcface", shape, entry), _dev(wt), _dev(bias), _dev(slope), _dev(s2), _dev(b2)
+    x, dw, db, dsl, ds2, db2 = (MC.dev(v) for v in (S.stem_raw("arcface", shape, entry), wt, bias, slope, s2, b2))
     n = b * h * w * 64
-    out, out2, solo = _Out(n, 16), _Out(n, 16), _Out(n, 16)
+    out, out2, solo = MC.Guarded(n, 2), MC.Guarded(n, 2), MC.Guarded(n, 2)
     L.check(lib.idb_arcface_stem(x.data_ptr(), int(entry == "u8"), b, h, w, dw.data_ptr(), db.data_ptr(), dsl.data_ptr(), ds2.data_ptr(), db2.data_ptr(),
-                                 out.ptr, out2.ptr, IDB[dt], _stream()), what)
+                                 out.ptr, out2.ptr, MC.IDB[dt], MC.stream()), what)
     L.check(lib.idb_arcface_stem(x.data_ptr(), int(entry == "u8"), b, h, w, dw.data_ptr(), db.data_ptr(), dsl.data_ptr(), None, None,
-                                 solo.ptr, None, IDB[dt], _stream()), what)
+                                 solo.ptr, None, MC.IDB[dt], MC.stream()), what)
     torch.cuda.synchronize()
     (got, bits), (got2, bits2), (_, bits_solo) = out.T(what, dt), out2.T(what, dt), solo.T(what, dt)
     ref, bound, _ = S.stem_reference("arcface", shape, entry, dt)
-    _judge(f"idb_arcface_stem {dt}", what, got.reshape(ref.shape), ref, bound)
+    W.judge(f"idb_arcface_stem {dt}", what, got.reshape(ref.shape), ref, bound)
     assert np.isfinite(got2).all(), f"{what}: out2 has elements that were not written"
     want2 = S.to_bits(S.out2_of(got.reshape(-1, 64), s2, b2, dt), dt).reshape(-1)
     diff = np.argwhere(bits2 != want2)
@@ -125,13 +70,13 @@ def test_pose_stem(lib, shape, entry, dt):
     what = f"idb_pose_stem {shape} {entry} {dt}"
     b, h, w = shape
     wt, bias, _, _, _ = S.stem_params("pose")
-    x, dw, db = _stem_input("pose", shape, entry), _dev(wt), _dev(bias)
+    x, dw, db = (MC.dev(v) for v in (S.stem_raw("pose", shape, entry), wt, bias))
     ref, bound, _ = S.stem_reference("pose", shape, entry, dt)
     assert ref.shape == (b, (h + 1) // 2, (w + 1) // 2, 64)
-    out = _Out(ref.size, 16)
-    L.check(lib.idb_pose_stem(x.data_ptr(), int(entry == "u8"), b, h, w, dw.data_ptr(), db.data_ptr(), out.ptr, IDB[dt], _stream()), what)
+    out = MC.Guarded(ref.size, 2)
+    L.check(lib.idb_pose_stem(x.data_ptr(), int(entry == "u8"), b, h, w, dw.data_ptr(), db.data_ptr(), out.ptr, MC.IDB[dt], MC.stream()), what)
     torch.cuda.synchronize()
-    _judge(f"idb_pose_stem {dt}", what, out.T(what, dt)[0].reshape(ref.shape), ref, bound)
+    W.judge(f"idb_pose_stem {dt}", what, out.T(what, dt)[0].reshape(ref.shape), ref, bound)
 
 
 # ---- idb_conv_in ---------------------------------------------------------------------------------------------------------------------
@@ -141,16 +86,16 @@ def test_conv_in(lib, case, dt):
     what = f"idb_conv_in {case.name} {dt}"
     b, cin, h, w, cout, rep = case.shape
     x, wt, bias, pre_w, pre_b = S.conv_in_inputs(case)
-    dx, dw, db = _dev(x), _dev(wt), _dev(bias)
-    dpw, dpb = (_dev(pre_w), _dev(pre_b)) if case.pre else (None, None)
+    dx, dw, db = MC.dev(x), MC.dev(wt), MC.dev(bias)
+    dpw, dpb = (MC.dev(pre_w), MC.dev(pre_b)) if case.pre else (None, None)
     ref, bound = S.conv_in_reference(case, dt)
     assert ref.shape == (rep, b, h, w, cout)
-    out = _Out(ref.size, 16)
+    out = MC.Guarded(ref.size, 2)
     L.check(lib.idb_conv_in(dx.data_ptr(), dw.data_ptr(), db.data_ptr(), out.ptr, b, rep, cin, h, w, cout, case.in_scale,
-                            dpw.data_ptr() if case.pre else None, dpb.data_ptr() if case.pre else None, IDB[dt], _stream()), what)
+                            dpw.data_ptr() if case.pre else None, dpb.data_ptr() if case.pre else None, MC.IDB[dt], MC.stream()), what)
     torch.cuda.synchronize()
     got, bits = out.T(what, dt)
-    _judge(f"idb_conv_in {dt}", what, got.reshape(ref.shape), ref, bound)
+    W.judge(f"idb_conv_in {dt}", what, got.reshape(ref.shape), ref, bound)
     bits = bits.reshape(rep, -1)
     assert all(np.array_equal(bits[0], bits[r]) for r in range(rep)), f"{what}: the copies of `rep` differ"
 
@@ -161,12 +106,12 @@ def test_linear_f32(lib, case):
     what = f"idb_linear_f32 {case.name}"
     m, n, k = case.shape
     x, wt, bias = S.linear_inputs(case)
-    dx, dw, db = _dev(x), _dev(wt), (None if bias is None else _dev(bias))
-    out = _Out(m * n)
-    L.check(lib.idb_linear_f32(dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), out.ptr, m, n, k, int(case.silu), _stream()), what)
+    dx, dw, db = MC.dev(x), MC.dev(wt), (None if bias is None else MC.dev(bias))
+    out = MC.Guarded(m * n)
+    L.check(lib.idb_linear_f32(dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), out.ptr, m, n, k, int(case.silu), MC.stream()), what)
     torch.cuda.synchronize()
     ref, bound = S.linear_reference(case)
-    _judge("idb_linear_f32" + (" silu_in" if case.silu else ""), what, out.f32(what).reshape(m, n), ref, bound)
+    W.judge("idb_linear_f32" + (" silu_in" if case.silu else ""), what, out.f32(what).reshape(m, n), ref, bound)
 
 
 # ---- idb_arcface_head ----------------------------------------------------------------------------------------------------------------
@@ -176,15 +121,15 @@ def test_arcface_head(lib, case, dt):
     what = f"idb_arcface_head {case.name} {dt}"
     m, n, k = case.shape
     x, wt, bias = S.head_inputs(case.shape, dt)
-    dx, dw, db = _dev_T(x, dt), _dev(wt), (_dev(bias) if case.bias else None)
+    dx, dw, db = MC.dev(S.to_bits(x, dt)), MC.dev(wt), (MC.dev(bias) if case.bias else None)
     need = lib.idb_arcface_head_workspace_bytes(m, n, k)
     assert need == S.head_workspace_bytes(m, n, k) and need % 4 == 0
-    out, ws = _Out(m * n), _Out(need // 4)
-    L.check(lib.idb_arcface_head(dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), out.ptr, m, n, k, IDB[dt], ws.ptr, need,
-                                 _stream()), what)
+    out, ws = MC.Guarded(m * n), MC.Guarded(need // 4)
+    L.check(lib.idb_arcface_head(dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), out.ptr, m, n, k, MC.IDB[dt], ws.ptr, need,
+                                 MC.stream()), what)
     torch.cuda.synchronize()
     ref, bound = S.head_reference(case, dt)
-    _judge(f"idb_arcface_head {dt}", what, out.f32(what).reshape(m, n), ref, bound)
+    W.judge(f"idb_arcface_head {dt}", what, out.f32(what).reshape(m, n), ref, bound)
     assert np.isfinite(ws.f32(what + " workspace")).all(), f"{what}: a workspace element of a slice was not written"
 
 
@@ -195,29 +140,28 @@ def test_pose_head(lib, shape, dt):
     what = f"idb_pose_head {shape} {dt}"
     b, hw, c = shape
     x, wt, bias = S.phead_inputs(shape, dt)
-    dx, dw, db = _dev_T(x, dt), _dev(wt), _dev(bias)
+    dx, dw, db = MC.dev(S.to_bits(x, dt)), MC.dev(wt), MC.dev(bias)
     assert dx.data_ptr() % 16 == 0
-    rot, ang = _Out(b * 9), _Out(b * 3)
-    L.check(lib.idb_pose_head(dx.data_ptr(), b, hw, c, dw.data_ptr(), db.data_ptr(), rot.ptr, ang.ptr, IDB[dt], _stream()), what)
+    rot, ang = MC.Guarded(b * 9), MC.Guarded(b * 3)
+    L.check(lib.idb_pose_head(dx.data_ptr(), b, hw, c, dw.data_ptr(), db.data_ptr(), rot.ptr, ang.ptr, MC.IDB[dt], MC.stream()), what)
     torch.cuda.synchronize()
     r64, tol_r, a64, tol_a, _ = S.phead_reference(shape, dt)
-    _judge(f"idb_pose_head R {dt}", what + " R", rot.f32(what).reshape(b, 9), r64, tol_r)
-    _judge(f"idb_pose_head angles {dt}", what + " angles", ang.f32(what).reshape(b, 3), a64, tol_a)
+    W.judge(f"idb_pose_head R {dt}", what + " R", rot.f32(what).reshape(b, 9), r64, tol_r)
+    W.judge(f"idb_pose_head angles {dt}", what + " angles", ang.f32(what).reshape(b, 3), a64, tol_a)
 
 
 # ---- idb_timestep_sinusoid -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,dim", S.SIN_SHAPES)
 def test_timestep_sinusoid(lib, n, dim):
     what = f"idb_timestep_sinusoid n {n} dim {dim}"
-    t = _dev(S.sin_inputs(n))
-    out = _Out(n * dim)
-    L.check(lib.idb_timestep_sinusoid(t.data_ptr(), out.ptr, n, dim, _stream()), what)
+    t = MC.dev(S.sin_inputs(n))
+    out = MC.Guarded(n * dim)
+    L.check(lib.idb_timestep_sinusoid(t.data_ptr(), out.ptr, n, dim, MC.stream()), what)
     torch.cuda.synchronize()
     ref, bar, emu = S.sin_bound(n, dim)
     print(f"{what}: bar {bar:.3e} (emulation {emu:.3e})")
-    _judge("idb_timestep_sinusoid", what, out.f32(what).reshape(n, dim), ref, bar)
+    W.judge("idb_timestep_sinusoid", what, out.f32(what).reshape(n, dim), ref, bar)
 
 
 def test_summary():
-    for k in sorted(_WORST):
-        print(f"stem matrix: {k}: worst err / bound {_WORST[k][0]:.4f} ({_WORST[k][1]})")
+    W.show()
