@@ -923,6 +923,49 @@ int idb_sgd_clip_step_table(int32_t count, float* const* weights, const float* c
                             double lr, double momentum, double weight_decay, double max_norm, int32_t first_step, double* total_norm,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * LoRA fine-tuning of one attention module (train_ID-Booth.py: rank-4 adapters on to_q / to_k / to_v / to_out.0): the attention that
+ * saves its row statistic, its backward, and the adapter gradients.  Layouts as idb_attention: q, out, dout, dq [batch][n_q][heads*64]
+ * with a row stride each; k, v, dk, dv [batch][n_kv_alloc][...] with one row stride per pair, only the first n_kv rows attended; the
+ * packed [q|k|v] buffer (stride 3 * heads * 64) serves for the inputs and, another one, for the gradients.  f16 / bf16 operands, fp32
+ * accumulation; no atomics and no inter-workgroup waiting anywhere: every result is bit-identical from run to run.
+ *   idb_attention_fwd_train: idb_attention without the causal mask, plus lse[batch][heads][n_q] (fp32) = ln sum_j exp(scale q.k_j).
+ *   idb_attention_bwd: with delta_i = sum_d dout out (fp32), P = exp(scale Q K^T - lse), dP = dout V^T, dS = P o (dP - delta):
+ *       dV = P^T dout, dQ = scale dS K, dK = scale dS^T Q; P and dS are rounded to the operand dtype for these products, each gradient
+ *       is summed in fp32 and rounded once.  Rows n_kv .. n_kv_alloc - 1 of k and v are never read and those of dk and dv never
+ *       written.  dQ comes from a kernel that owns query blocks of 128 rows and recomputes S (no sum across workgroups exists); dK and
+ *       dV from one that owns key blocks of IDB_ATTN_BWD_KEY_BLOCK keys and sweeps the queries in slices of IDB_ATTN_BWD_SLICE rows:
+ *       form 0 sweeps all of them; form 1 (fewer than IDB_ATTN_BWD_FULL_GRID key-block workgroups and more than two slices) cuts the
+ *       query range into chunks of `query_rows` rows, whose fp32 slabs in the workspace a plain pass sums in ascending order.
+ *       launches: 3 (form 0) or 4.  A gradient may not share a byte with an input or the workspace.
+ *   idb_lora_grad: x [m][in] and dy [m][out] in the operand dtype (row strides x_ld, dy_ld: dy may be a column slice of the packed
+ *       gradient buffer), lora_a [rank][in] and lora_b [out][rank] fp32 (peft's layouts); db[out][rank] = scale dy^T (x A^T) and
+ *       da[rank][in] = scale (dy B)^T x in fp32.  The out x in weight gradient is never formed.  The sum over m runs in fp32 within
+ *       chunks of IDB_LORA_GRAD_CHUNK_ROWS rows (more once m exceeds that times IDB_LORA_GRAD_MAX_CHUNKS), the chunks merged in
+ *       ascending order in double and rounded once.  rank 1..IDB_LORA_MAX_RANK; in and out multiples of 64.
+ * Refusals (IDB_EINVAL, a dtype other than f16 / bf16: IDB_EUNSUPPORTED) name the argument and come before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define IDB_ATTN_BWD_KEY_BLOCK 128
+#define IDB_ATTN_BWD_SLICE 32
+#define IDB_ATTN_BWD_FULL_GRID 128
+#define IDB_LORA_MAX_RANK 16
+#define IDB_LORA_GRAD_CHUNK_ROWS 32
+#define IDB_LORA_GRAD_MAX_CHUNKS 256
+int idb_attention_fwd_train(const void* q, int32_t q_ld, const void* k, const void* v, int32_t kv_ld, void* out, int32_t out_ld, float* lse,
+                            int32_t batch, int32_t heads, int32_t n_q, int32_t n_kv, int32_t n_kv_alloc, float scale, int32_t dtype,
+                            void* stream);
+size_t idb_attention_bwd_workspace_bytes(int32_t batch, int32_t heads, int32_t n_q, int32_t n_kv);
+int idb_attention_bwd_plan(int32_t batch, int32_t heads, int32_t n_q, int32_t n_kv, int32_t* form, int32_t* key_block, int32_t* query_rows,
+                           int32_t* launches);
+int idb_attention_bwd(const void* q, int32_t q_ld, const void* k, const void* v, int32_t kv_ld, const void* out, int32_t out_ld,
+                      const void* dout, int32_t dout_ld, const float* lse, void* dq, int32_t dq_ld, void* dk, void* dv, int32_t dkv_ld,
+                      void* workspace, size_t workspace_bytes, int32_t batch, int32_t heads, int32_t n_q, int32_t n_kv, int32_t n_kv_alloc,
+                      float scale, int32_t dtype, void* stream);
+size_t idb_lora_grad_workspace_bytes(int64_t m, int32_t in, int32_t out, int32_t rank);
+int idb_lora_grad(const void* x, int32_t x_ld, const void* dy, int32_t dy_ld, const float* lora_a, const float* lora_b, float* da, float* db,
+                  int64_t m, int32_t in, int32_t out, int32_t rank, float scale, void* workspace, size_t workspace_bytes, int32_t dtype,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
