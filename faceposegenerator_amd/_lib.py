@@ -23,6 +23,7 @@ IDB_SGD_CLIP_WS_BYTES = 65536
 IDB_SGD_CLIP_MAX_TENSORS = 8
 IDB_ATTN_BWD_KEY_BLOCK, IDB_ATTN_BWD_SLICE, IDB_ATTN_BWD_FULL_GRID = 128, 32, 128
 IDB_LORA_MAX_RANK, IDB_LORA_GRAD_CHUNK_ROWS, IDB_LORA_GRAD_MAX_CHUNKS = 16, 32, 256
+IDB_ADAMW_TABLE_MAX = 1024
 IDB_PAIR_DIST2, IDB_PAIR_KNN, IDB_PAIR_PRDC, IDB_PAIR_NEAREST, IDB_PAIR_POLY = 0, 1, 2, 3, 4
 # the selected points of idb_verif_roc, in the order of its points / ints outputs
 IDB_VERIF_POINTS = ("eer_t2", "eer_t1", "fmr0", "fmr1000", "fmr100", "fmr20", "fmr10", "fnmr0", "fnmr100", "fnmr1000", "youden", "mcc", "first")
@@ -57,6 +58,7 @@ EXPORTS = [
     "idb_sgd_clip_table_workspace_bytes", "idb_sgd_clip_step_table",
     "idb_attention_fwd_train", "idb_attention_bwd_workspace_bytes", "idb_attention_bwd_plan", "idb_attention_bwd",
     "idb_lora_grad_workspace_bytes", "idb_lora_grad",
+    "idb_layernorm_bwd", "idb_geglu_fwd", "idb_geglu_bwd", "idb_adamw_clip_table_workspace_bytes", "idb_adamw_clip_step_table",
 ]
 
 
@@ -241,6 +243,11 @@ def load() -> C.CDLL:
                                         i32, vp]),
         "idb_lora_grad_workspace_bytes": (sz, [i64, i32, i32, i32]),
         "idb_lora_grad": (C.c_int, [vp, i32, vp, i32, vp, vp, vp, vp, i64, i32, i32, i32, f32, vp, sz, i32, vp]),
+        "idb_layernorm_bwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, f32, i32, vp]),
+        "idb_geglu_fwd": (C.c_int, [vp, i32, vp, i64, i32, i32, vp]),
+        "idb_geglu_bwd": (C.c_int, [vp, i32, vp, vp, i64, i32, i32, vp]),
+        "idb_adamw_clip_table_workspace_bytes": (sz, [i32]),
+        "idb_adamw_clip_step_table": (C.c_int, [i32, vp, vp, vp, vp, vp] + [C.c_double] * 7 + [i64, vp, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

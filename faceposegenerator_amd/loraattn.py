@@ -6,8 +6,8 @@ with a bias, Dropout(0)) with peft ``lora.Linear`` adapters (scaling = alpha / r
 (``idb_lora_merge``, rebuilt by ``refresh()`` whenever the adapters change) through ``idb_gemm`` and ``idb_attention_fwd_train``; that is
 mathematically peft's unmerged training forward, rounded differently.  The backward is ``idb_attention_bwd``, ``idb_gemm`` with the
 transposed merged weights for the input gradients, and ``idb_lora_grad`` for the eight adapter gradients; the out x in weight gradients
-are never formed.  Backward of the surrounding block (LayerNorm, GEGLU, GroupNorm, convolutions, the loss) and an optimiser are not
-here.  There is no CPU fallback."""
+are never formed.  The surrounding transformer block (LayerNorm, GEGLU, the residuals) and the optimiser are lorablock.py's; the
+backward of GroupNorm, the convolutions and the loss is not built.  There is no CPU fallback."""
 from __future__ import annotations
 
 import math
@@ -186,13 +186,13 @@ class LoRAAttention:
             else:
                 self.w_bwd["kv"][:, (j - 1) * c:j * c].copy_(tmp)
 
-    def _gemm(self, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """out[m][n] = x[m][k] w[n][k]^T (+ bias) through idb_gemm; x dense."""
+    def _gemm(self, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """out[m][n] = x[m][k] w[n][k]^T (+ bias) (+ residual [m][n], in the epilogue: one rounding) through idb_gemm; x dense."""
         n, k = w.shape
         m = x.numel() // k
         out = torch.empty((m, n), dtype=self.dtype, device=self.device)
         d = L.gemm_desc(self.dt, [(x.data_ptr(), k, 1, 1, 1)], w.data_ptr(), n, m, 1, 1, out=out.data_ptr(),
-                        bias=None if bias is None else bias.data_ptr())
+                        bias=None if bias is None else bias.data_ptr(), residual=None if residual is None else residual.data_ptr())
         L.check(L.run_gemm(self.lib, d, self._workspace, self._stream()), "idb_gemm")
         return out
 
@@ -209,8 +209,14 @@ class LoRAAttention:
             raise ValueError(f"LoRAAttention: context must be [batch][tokens][{self.context_dim}] {self.dtype} on {self.device}")
 
     # ---- forward and backward -------------------------------------------------------------------------------------------------------
-    def __call__(self, x: torch.Tensor, context: Optional[torch.Tensor] = None) -> AttnOut:
+    def __call__(self, x: torch.Tensor, context: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> AttnOut:
+        """`residual` ([batch][tokens][channels], the block's residual stream) is added in the to_out GEMM's epilogue: `out` is then the
+        sum, rounded once.  The backward is unchanged: the gradient of the sum is the gradient of the module's own output."""
         self._check_inputs(x, context)
+        if residual is not None:
+            if residual.shape != x.shape or residual.dtype != self.dtype or residual.device != self.device:
+                raise ValueError("LoRAAttention: residual must match x's shape, dtype and device")
+            residual = residual.contiguous()
         x = x.contiguous()
         b, n, c = x.shape
         h, es = self.heads, 2
@@ -226,7 +232,7 @@ class LoRAAttention:
         lse = torch.empty((b, h, n), dtype=torch.float32, device=self.device)
         L.check(self.lib.idb_attention_fwd_train(qp, q_ld, kp, vp, kv_ld, attn.data_ptr(), c, lse.data_ptr(), b, h, n, n_kv, n_kv, 0.125, self.dt,
                                                  self._stream()), "idb_attention_fwd_train")
-        out = self._gemm(attn, self.w_fwd["out"], self.bias).view(b, n, c)
+        out = self._gemm(attn, self.w_fwd["out"], self.bias, residual).view(b, n, c)
         return AttnOut(out, x, context, q, kv, attn, lse)
 
     def _lora_grad(self, grads: SD, name: str, x: torch.Tensor, dy_ptr: int, dy_ld: int, m: int) -> None:

@@ -966,6 +966,41 @@ int idb_lora_grad(const void* x, int32_t x_ld, const void* dy, int32_t dy_ld, co
                   int64_t m, int32_t in, int32_t out, int32_t rank, float scale, void* workspace, size_t workspace_bytes, int32_t dtype,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * LoRA fine-tuning of one transformer block (diffusers' BasicTransformerBlock, SD-2.1's form): what the block's backward needs
+ * besides the attention modules above, and the optimiser step of the adapters.  f16 / bf16 operands, fp32 arithmetic, every result
+ * rounded once; no atomics and no inter-workgroup waiting: bit-identical from run to run (csrc/idb_tblock.hip, csrc/idb_adamw.hip).
+ *   idb_layernorm_bwd: the input gradient of idb_layernorm.  x [rows][c] is the forward's raw input; mean, rstd and xhat are
+ *       recomputed with the forward's own arithmetic (no statistic is saved).  With g = dy gamma:
+ *       dx = rstd (g - mean(g) - xhat mean(g xhat)) (+ add), rounded once.  add: an operand-dtype tensor of dx's shape (the residual
+ *       stream's gradient) or NULL.  dx may be add or dy themselves (a wave owns whole rows and reads them before it stores), nothing
+ *       else.  c a multiple of 8, at most 1536, as idb_layernorm.  d_gamma and d_beta are NOT computed: LayerNorm's affine is frozen
+ *       in this fine-tuning (peft marks only the adapters trainable).
+ *   idb_geglu_fwd: hg [rows][2 inner] (row stride hg_ld), value then gate, diffusers' order (hidden, gate = proj(x).chunk(2, -1));
+ *       out[rows][inner] = value gelu(gate), the exact-GELU approximation of idb_gemm's GEGLU epilogue.
+ *   idb_geglu_bwd: dhg[rows][2 inner] dense: dvalue = dout gelu(gate), dgate = dout value (Phi(gate) + gate phi(gate)), Phi the
+ *       same approximation, phi sharing its exponential.  inner a multiple of 8; rows * inner / 8 below 2^31.
+ *   idb_adamw_clip_step_table: GradScaler.unscale_ + clip_grad_norm_(params, max_norm) + torch.optim.AdamW(non-amsgrad).step() over
+ *       1..1024 fp32 tensors whose pointer and numel tables (count entries each) lie in DEVICE memory, as idb_sgd_clip_step_table's
+ *       (the same norm arithmetic and geometry).  total_norm = inv_scale ||g|| in double.  Per element, in double from the fp32
+ *       states, each fp32 state rounded once: g^ = coef inv_scale g, coef = min(1, max_norm / (total_norm + 1e-6));
+ *       w <- w (1 - lr weight_decay); m <- beta1 m + (1 - beta1) g^; v <- beta2 v + (1 - beta2) g^2;
+ *       w <- w - (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps).  step >= 1 is the number of this step; the two
+ *       bias corrections are computed on the host in double.  If total_norm is not finite nothing is written to w, m, v and
+ *       *skipped = 1 (GradScaler.step's skip), otherwise 0; the scale's growth and backoff stay the caller's.  total_norm (double)
+ *       and skipped (int32) are device memory.  ws: idb_adamw_clip_table_workspace_bytes(count), 16-byte aligned.  The tables'
+ *       contents cannot be validated on the host: the caller guarantees 1 <= numel <= 2^32 and distinct buffers.  Three launches.
+ * Refusals (IDB_EINVAL, a dtype other than f16 / bf16: IDB_EUNSUPPORTED) name the argument and come before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int idb_layernorm_bwd(const void* x, const void* dy, const void* add, const float* gamma, void* dx, int64_t rows, int32_t c, float eps,
+                      int32_t dtype, void* stream);
+int idb_geglu_fwd(const void* hg, int32_t hg_ld, void* out, int64_t rows, int32_t inner, int32_t dtype, void* stream);
+int idb_geglu_bwd(const void* hg, int32_t hg_ld, const void* dout, void* dhg, int64_t rows, int32_t inner, int32_t dtype, void* stream);
+size_t idb_adamw_clip_table_workspace_bytes(int32_t count);
+int idb_adamw_clip_step_table(int32_t count, float* const* weights, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                              const int64_t* numel, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                              double inv_scale, int64_t step, double* total_norm, int32_t* skipped, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
