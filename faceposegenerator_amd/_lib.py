@@ -59,6 +59,7 @@ EXPORTS = [
     "idb_attention_fwd_train", "idb_attention_bwd_workspace_bytes", "idb_attention_bwd_plan", "idb_attention_bwd",
     "idb_lora_grad_workspace_bytes", "idb_lora_grad",
     "idb_layernorm_bwd", "idb_geglu_fwd", "idb_geglu_bwd", "idb_adamw_clip_table_workspace_bytes", "idb_adamw_clip_step_table",
+    "idb_groupnorm_bwd_workspace_bytes", "idb_groupnorm_bwd_plan", "idb_groupnorm_bwd",
 ]
 
 
@@ -248,6 +249,9 @@ def load() -> C.CDLL:
         "idb_geglu_bwd": (C.c_int, [vp, i32, vp, vp, i64, i32, i32, vp]),
         "idb_adamw_clip_table_workspace_bytes": (sz, [i32]),
         "idb_adamw_clip_step_table": (C.c_int, [i32, vp, vp, vp, vp, vp] + [C.c_double] * 7 + [i64, vp, vp, vp, sz, vp]),
+        "idb_groupnorm_bwd_workspace_bytes": (sz, [i32, i32, i32]),
+        "idb_groupnorm_bwd_plan": (C.c_int, [i32] * 5 + [C.POINTER(i32)] * 5),
+        "idb_groupnorm_bwd": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, f32, i32, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing

@@ -13,7 +13,7 @@ linearly to every gradient.
 
 ``LoRAAdamW`` is ``GradScaler.unscale_`` + ``clip_grad_norm_`` + ``torch.optim.AdamW.step`` on the fp32 adapter masters as one library
 call (``idb_adamw_clip_step_table``), ``cosine_lr`` the reference's schedule.  The convolutions and GroupNorms between the UNet's blocks
-have no backward here.  There is no CPU fallback."""
+have their backward in lorastage.py.  There is no CPU fallback."""
 from __future__ import annotations
 
 import math
@@ -238,6 +238,9 @@ def _owners(block_or_layers) -> List[LoRAAttention]:
     items = block_or_layers if isinstance(block_or_layers, (list, tuple)) else [block_or_layers]
     out: List[LoRAAttention] = []
     for it in items:
+        if not isinstance(it, (LoRATransformerBlock, LoRAAttention)) and hasattr(it, "layers"):      # lorastage's LoRATransformer2D / LoRAStage
+            out.extend(it.layers)
+            continue
         out.extend(it.layers if isinstance(it, LoRATransformerBlock) else [it])
     if not out or not all(isinstance(a, LoRAAttention) for a in out):
         raise ValueError("LoRAAdamW: takes a LoRATransformerBlock, a LoRAAttention, or a list of them")

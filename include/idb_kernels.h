@@ -1001,6 +1001,38 @@ int idb_adamw_clip_step_table(int32_t count, float* const* weights, const float*
                               const int64_t* numel, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
                               double inv_scale, int64_t step, double* total_norm, int32_t* skipped, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * LoRA fine-tuning across UNet stages: the input gradient of idb_groupnorm (diffusers' ResnetBlock2D.norm1 / norm2 with the SiLU that
+ * follows them, Transformer2DModel.norm without), csrc/idb_gnbwd.hip.  The convolutions' and Linears' input gradients are idb_gemm
+ * with flipped / transposed weights (faceposegenerator_amd/lorastage.py) and need no entry of their own.
+ *   x0 [batch][hw][c0], x1 [batch][hw][c1] or NULL (c1 == 0): the forward's RAW input(s), the channel concatenation x0 | x1.
+ *   stat_partials [batch][stat_chunks][groups][2] fp32: what idb_groupnorm_stats wrote for x0 | x1 (1 <= stat_chunks <= 64).
+ *   dy [batch][hw][c0 + c1] dense: the gradient w.r.t. the forward's output (after the SiLU when silu = 1).
+ *   add [batch][hw][c0 + c1] dense or NULL: added to dx (a residual's or shortcut's gradient, at no launch of its own).
+ *   dx0 [batch][hw][c0], dx1 [batch][hw][c1] (NULL exactly when c1 == 0).
+ * Per (sample, group), n = hw * channels per group: mean and rstd are formed from stat_partials with idb_groupnorm's own expressions
+ * (chunks summed in a fixed order in fp32, then in double mean = a / n, var = max(0, q / n - mean^2), rstd = 1 / sqrt(var + eps)).
+ * Per element xhat = (x - mean) rstd, y = xhat gamma + beta, d = dy (silu = 0) or dy s (1 + y (1 - s)) with s = 1 / (1 + exp(-y))
+ * (silu = 1; one v_exp_f32 and one v_rcp_f32), g = d gamma; m1 = sum g / n, m2 = sum g xhat / n;
+ * dx = rstd (g - m1 - xhat m2) (+ add), rounded once.  fp32 arithmetic; the two sums are fp32 per (sample, pixel chunk, group) in
+ * fixed-order trees and merged over the chunks in double in a fixed order.  Two launches (sums into the workspace, then dx), no
+ * atomics, no workgroup waits for another: bit-identical from run to run.  d_gamma and d_beta are NOT computed: GroupNorm's affine is
+ * frozen in this fine-tuning (peft marks only the adapters trainable).
+ * When c1 == 0, dx0 may be dy or add themselves (pass 1 has finished before pass 2 stores, and a thread of pass 2 has read the
+ * elements it writes); nothing else may overlap an output.  workspace: idb_groupnorm_bwd_workspace_bytes, 16-byte aligned.
+ * Limits are idb_groupnorm's: c0, c1 multiples of 8, groups dividing c0 + c1 with at least 2 channels per group, a slice of
+ * lcm(channels per group, 8) channels (doubled up to 8 vector columns) of at most 256 columns and 64 groups; eps > 0.
+ * Refusals (IDB_EINVAL; a dtype other than f16 / bf16: IDB_EUNSUPPORTED) name the argument and come before any HIP call.
+ * idb_groupnorm_bwd_plan is host-only: the same validation of the dims and what would be launched: slice_channels x slices = c0 + c1,
+ * chunks x chunk_len >= hw the pixel chunks of pass 1 (grid chunks x slices x batch), apply_blocks the pixel blocks of pass 2.
+ * ------------------------------------------------------------------------------------------ */
+size_t idb_groupnorm_bwd_workspace_bytes(int32_t batch, int32_t hw, int32_t groups);
+int idb_groupnorm_bwd_plan(int32_t c0, int32_t c1, int32_t batch, int32_t hw, int32_t groups, int32_t* slice_channels, int32_t* slices,
+                           int32_t* chunks, int32_t* chunk_len, int32_t* apply_blocks);
+int idb_groupnorm_bwd(const void* x0, int32_t c0, const void* x1, int32_t c1, const float* stat_partials, int32_t stat_chunks, const void* dy,
+                      const void* add, const float* gamma, const float* beta, float eps, int32_t silu, void* dx0, void* dx1, int32_t batch,
+                      int32_t hw, int32_t groups, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
